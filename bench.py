@@ -12,6 +12,12 @@ Multi-GPU (one process per GPU): every rank plans its own independent scene (wea
 data-path collective); value = cycles completed by all ranks / max-over-ranks wall time.  Rank
 0 prints ONE JSON line.  Under torchrun the ranks come from its env; `bench.py --gpus N` run
 alone starts the N ranks itself as one child torchrun (launch_ranks) before any GPU call.
+
+A plain run sets up, warms up, times `--steps` cycles and prints the headline line (metric,
+value, unit, ms_per_step, ...).  `--dump-outputs DIR` also writes the last timed step's outputs
+as DIR/<name>.npy (same arguments -> same inputs, so two builds compare output for output).
+`--full` adds every other measurement and check to the line: roofline, PCIe-inclusive cycle,
+ellipsoid parity, CPU baseline, c4_sharded, the planning-step / QP / MILP lines, roofline_sweep.
 """
 import argparse
 import glob
@@ -43,7 +49,17 @@ def parse(argv=None):
     ap.add_argument("--N", type=int, default=5000)
     ap.add_argument("--T", type=int, default=8)
     ap.add_argument("--seed", type=int, default=20251015)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check "
+                         "(roofline, PCIe-inclusive cycle, ellipsoid parity against the oracle, "
+                         "CPU baseline, c4_sharded, the planning-step / QP / MILP lines, "
+                         "roofline_sweep) and add them to the result line; a plain run times "
+                         "the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left in the cycle's "
+                         "output buffers (mean, cov, prob_lower, records) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the CPU baseline legs")
     ap.add_argument("--cpu-cycles", type=int, default=200)
     ap.add_argument("--graph", action="store_true",
                     help="time hipGraph replays of the cycle instead of direct C-ABI calls")
@@ -1052,6 +1068,39 @@ def spin_sync(local):
     return ok
 
 
+DUMP_CAP_BYTES = 64 << 20     # --dump-outputs writes at most this much in all
+
+
+def sample_rows(a, cap_bytes, seed=0):
+    """`a` itself when it fits in cap_bytes, else a fixed seeded sample of its rows (sorted
+    indices along axis 0, the same for every run of the same shape)."""
+    if a.nbytes <= cap_bytes or a.shape[0] <= 1:
+        return a
+    keep = max(1, int(cap_bytes // max(a.nbytes // a.shape[0], 1)))
+    idx = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=keep, replace=False))
+    return a[idx]
+
+
+def cycle_outputs(cyc):
+    """What a caller of the timed step holds after it: the cycle's output buffers as float64
+    arrays.  `records` is the half-space records one row each, their fields in HALFSPACE_DTYPE
+    order (the int32 fields are exact in float64)."""
+    h = cyc.records().reshape(-1)
+    return {"mean": cyc.mean.cpu().numpy(), "cov": cyc.cov.cpu().numpy(),
+            "prob_lower": cyc.prob_lower.cpu().numpy(),
+            "records": np.stack([h[n].astype(np.float64) for n in h.dtype.names], axis=1)}
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """Write `arrays` as dirname/<name>.npy (rank r > 0 of a multi-rank run: <name>_rank<r>),
+    DUMP_CAP_BYTES in all: an array over its share is cut to a fixed seeded sample of rows."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(world, 1) // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(sample_rows(np.asarray(a, np.float64), share))
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def main():
     args = parse()
     rc = launch_ranks(args)
@@ -1093,19 +1142,11 @@ def main():
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cycle_outputs(cyc), rank, world)
     h = cyc.records().reshape(-1)
     assert np.all(h["status"] == 0), "non-ok constraint records"
 
-    # dominant (and only) kernel of the cycle: moments_kernel<double,1,true> = the Gram
-    # reduction with the fused half-space tail; algorithmic bytes = every particle coordinate
-    # read once (2T float64 per particle) -- SURVEY.md 8d's 16 N T read term
-    n_part = int(sum(store.counts))
-    alg_bytes = n_part * 2 * args.T * 8
-    t_kernel = time_kernel_live(cyc.run, dev)
-    t_mom = time_kernel_live(lambda: engine.moments(store, cyc.mean, cyc.cov, cyc.ws), dev)
-
-    pcie = pcie_inclusive(cyc, step, dev)
-    traffic, traffic_src = pmc_traffic("void ccmpc::moments_kernel<double, 1, true", "C2")
     value = world * args.steps / elapsed
     out = {
         "metric": METRIC,
@@ -1133,25 +1174,51 @@ def main():
             "cells": store.n_cells, "halfspaces_per_cycle": cyc.n_constraints,
         },
         "constraints_per_s": round(value * cyc.n_constraints, 1),
-        "pcie_inclusive": pcie,
-        "roofline": {
-            "bound": "hbm",
-            "kernel": "moments_kernel<double,1,true> (ccmpc_minkowski_cycle: MFMA Gram + "
-                      "last-arriver combine + MVOE half-spaces, one launch)",
-            "achieved": round(alg_bytes / t_kernel / 1e9, 2),
-            "peak": HBM_PEAK / 1e9,
-            "unit": "GB/s",
-            "frac": round(alg_bytes / t_kernel / HBM_PEAK, 5),
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "alg_bytes_per_launch": alg_bytes,
-            "avg_launch_us": round(t_kernel * 1e6, 3),
-            "moments_only_avg_launch_us": round(t_mom * 1e6, 3),
-            "achievable_peak": HBM_ACHIEVABLE / 1e9,
-            "frac_of_achievable": round(alg_bytes / t_kernel / HBM_ACHIEVABLE, 5),
-            "note": "C2 is a latency chain (DESIGN.md 4.1); the HBM-bound configs are c4_sharded "
-                    "and roofline_sweep's C3 1e5 / C5 lines",
-        },
+    }
+    if args.full:
+        full_run(out, args, dev, world, rank, cyc, step, ovs, ref, h, value)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if _backend() is not None:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def full_run(out, args, dev, world, rank, cyc, step, ovs, ref, h, value):
+    """--full: every measurement and check beside the headline, added to `out` (the cycle's
+    roofline and PCIe-inclusive rate, parity against the oracle, the CPU baseline, c4_sharded,
+    the C4 batch rooflines, the planning-step / QP / MILP lines, roofline_sweep).  Every rank
+    takes part (c4_sharded's gather); `h` = the timed loop's records."""
+    from ccmpc import engine
+    store = cyc.store
+
+    # dominant (and only) kernel of the cycle: moments_kernel<double,1,true> = the Gram
+    # reduction with the fused half-space tail; algorithmic bytes = every particle coordinate
+    # read once (2T float64 per particle) -- SURVEY.md 8d's 16 N T read term
+    n_part = int(sum(store.counts))
+    alg_bytes = n_part * 2 * args.T * 8
+    t_kernel = time_kernel_live(cyc.run, dev)
+    t_mom = time_kernel_live(lambda: engine.moments(store, cyc.mean, cyc.cov, cyc.ws), dev)
+
+    out["pcie_inclusive"] = pcie_inclusive(cyc, step, dev)
+    traffic, traffic_src = pmc_traffic("void ccmpc::moments_kernel<double, 1, true", "C2")
+    out["roofline"] = {
+        "bound": "hbm",
+        "kernel": "moments_kernel<double,1,true> (ccmpc_minkowski_cycle: MFMA Gram + "
+                  "last-arriver combine + MVOE half-spaces, one launch)",
+        "achieved": round(alg_bytes / t_kernel / 1e9, 2),
+        "peak": HBM_PEAK / 1e9,
+        "unit": "GB/s",
+        "frac": round(alg_bytes / t_kernel / HBM_PEAK, 5),
+        "traffic": traffic,
+        "traffic_source": traffic_src,
+        "alg_bytes_per_launch": alg_bytes,
+        "avg_launch_us": round(t_kernel * 1e6, 3),
+        "moments_only_avg_launch_us": round(t_mom * 1e6, 3),
+        "achievable_peak": HBM_ACHIEVABLE / 1e9,
+        "frac_of_achievable": round(alg_bytes / t_kernel / HBM_ACHIEVABLE, 5),
+        "note": "C2 is a latency chain (DESIGN.md 4.1); the HBM-bound configs are c4_sharded "
+                "and roofline_sweep's C3 1e5 / C5 lines",
     }
     if rank == 0:
         out["ellipsoid_parity"] = ellipsoid_parity(ovs, ref, args.T, h)
@@ -1221,11 +1288,6 @@ def main():
             out["v8_milp"] = v8_milp(dev, with_cpu=not args.no_cpu)
     if not args.no_sweep and rank == 0:
         out["roofline_sweep"] = sweep(dev, args.seed)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if _backend() is not None:
-        import torch.distributed as dist
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

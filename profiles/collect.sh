@@ -14,7 +14,7 @@ OUT=$ROOT/gpurun_out/prof_$ROUND
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $ROOT/bench.py --no-cpu --steps 300 --warmup 30"
+BENCH="python3 $ROOT/bench.py --full --no-cpu --steps 300 --warmup 30"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- $BENCH > "$OUT/trace_bench.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/fetch" -o run --output-format csv -- $BENCH > "$OUT/fetch_bench.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/write" -o run --output-format csv -- $BENCH > "$OUT/write_bench.log" 2>&1

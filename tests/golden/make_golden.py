@@ -390,12 +390,14 @@ def pin_ovehicles_and_l4(rng):
             out["A"].append(A_k)
             out["b"].append(b_k)
             out["yaw_mean"].append(m_k)
-    np.savez(os.path.join(HERE, "ovehicle_l4.npz"), T=T, minpos=minpos, bbox=bbox,
-             pred=np.array(preds), z=np.array(zs), latent_pmf=np.array(pmfs),
-             past=np.array(pasts), K=np.array(out["K"]), counts=np.array(out["counts"]),
-             positions=np.concatenate(out["positions"]), yaws=np.concatenate(out["yaws"]),
-             pmf_out=pmf_out, init_center=centre, A=np.array(out["A"]), b=np.array(out["b"]),
-             yaw_mean=np.array(out["yaw_mean"]))
+    # compressed: the plain archive is over the 1 MiB limit for a committed file
+    np.savez_compressed(
+        os.path.join(HERE, "ovehicle_l4.npz"), T=T, minpos=minpos, bbox=bbox,
+        pred=np.array(preds), z=np.array(zs), latent_pmf=np.array(pmfs),
+        past=np.array(pasts), K=np.array(out["K"]), counts=np.array(out["counts"]),
+        positions=np.concatenate(out["positions"]), yaws=np.concatenate(out["yaws"]),
+        pmf_out=pmf_out, init_center=centre, A=np.array(out["A"]), b=np.array(out["b"]),
+        yaw_mean=np.array(out["yaw_mean"]))
 
 
 def scipy_mod():
