@@ -17,6 +17,8 @@ CCMPC_OK = 0
 CCMPC_F64 = 0
 CCMPC_F32 = 1
 GMM_PER_LATENT, GMM_PER_PARTICLE = 0, 1
+# record kinds (CCMPC_REC_KIND_*)
+REC_KIND_HALFSPACE, REC_KIND_AFFINE, REC_KIND_HALFSPACE_COMPACT, REC_KIND_AFFINE_COMPACT = range(4)
 
 STATUS = {
     0: "ok", -1: "invalid argument", -2: "kernel launch failed", -3: "workspace too small",
@@ -134,6 +136,8 @@ SIGNATURES = {
     "ccmpc_mpc_qp_ltv": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P,
                                         ctypes.c_int, _P, _I64, _P, ctypes.c_int, _I32, _D, _P,
                                         _SZ, _P, _P, _P, _P, _P, _P]),
+    "ccmpc_risk_audit": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64, _I64, _P,
+                                        _P, _P, ctypes.c_int, _D, _P, _P, _P, _P, _P, _P]),
     "ccmpc_selftest": (ctypes.c_int, [ctypes.c_int, _I64, _P, _P, _D, _I32, _P]),
     "ccmpc_poison_lds": (ctypes.c_int, [_D, _P]),
 }

@@ -148,6 +148,13 @@ class MinkowskiCycle:
     def records(self):
         return engine.halfspaces(self.rec)
 
+    def audit(self, plan, cell_plan=None, out=None):
+        """Monte-Carlo audit (engine.risk_audit) of `plan` and of this cycle's half-spaces on
+        its own particle store, at its R.  Call after run() / replay()."""
+        return engine.risk_audit(self.store, plan=plan, rec=self.rec,
+                                 rec_kind=engine._lib.REC_KIND_HALFSPACE, R=self.R,
+                                 cell_plan=cell_plan, out=out)
+
 
 class AffineCycle:
     def __init__(self, store, K, ref_traj, ph=None, R=risk.R_COLLISION, scene_K=None,
@@ -183,3 +190,10 @@ class AffineCycle:
 
     def records(self):
         return engine.affine_records(self.rec)
+
+    def audit(self, plan, cell_plan=None, out=None):
+        """Monte-Carlo audit (engine.risk_audit) of `plan` and of this cycle's affine
+        half-spaces on its own particle store, at its R.  Call after run()."""
+        return engine.risk_audit(self.store, plan=plan, rec=self.rec,
+                                 rec_kind=engine._lib.REC_KIND_AFFINE, R=self.R,
+                                 cell_plan=cell_plan, out=out)

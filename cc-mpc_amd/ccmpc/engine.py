@@ -4,13 +4,14 @@ PyTorch is used only for device memory, streams and graphs; every numeric step i
 in libccmpc.so.  All functions enqueue on torch's current stream and never synchronise, so a
 whole constraint-generation cycle can be captured into a hipGraph (torch.cuda.CUDAGraph).
 """
+import collections
 import ctypes
 import os
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, risk
 
 F64, F32 = _lib.CCMPC_F64, _lib.CCMPC_F32
 
@@ -632,6 +633,117 @@ def halfspaces(rec_bytes):
 def affine_records(rec_bytes):
     return rec_bytes.cpu().numpy().reshape(-1).view(_lib.AFFINE_DTYPE).reshape(
         rec_bytes.shape[:-1])
+
+
+RiskAudit = collections.namedtuple("RiskAudit", "hit hit_any min_d2 rec_open open")
+RiskAudit.__doc__ = """risk_audit's device tensors: hit [C, T] int64, hit_any [C] int64, min_d2
+[C, T] float64 (None without a plan); rec_open [C, P] int64, open [C, T] int64 (None without
+records).  See ccmpc_risk_audit in include/ccmpc.h for what each counts."""
+
+
+def _audit_rows(rec_kind, T):
+    half = rec_kind in (_lib.REC_KIND_HALFSPACE, _lib.REC_KIND_HALFSPACE_COMPACT)
+    return T * (T - 1) // 2 if half else T
+
+
+def risk_audit(store, plan=None, rec=None, rec_kind=None, R=risk.R_COLLISION, cell_plan=None,
+               T=None, out=None):
+    """Monte-Carlo audit of a plan and / or constraint records on a ParticleStore
+    (ccmpc_risk_audit): per cell, the particles the plan passes within R of, and the particles
+    each record (and all records of a step together) leave unprotected.
+
+    plan: device float64 tensor (T, >= 2) or (n_plans, T, >= 2) -- ego positions in the first
+    two columns, e.g. the QP's X_star / out_x; cell_plan: each cell's plan row (None: row 0) as
+    a host sequence (range-checked here) or an int32 device tensor [C] (read unchecked).
+    rec: the (C, P, 128) uint8 records a cycle holds (rec_kind REC_KIND_HALFSPACE / _AFFINE) or
+    their (C, P, 32) compact packing (the _COMPACT kinds).  T: the audited horizon (default
+    store.T; fewer steps read only the first planes).
+    out: a previous RiskAudit whose buffers are written again (nothing is allocated then, so the
+    call can be captured).  A plan that is not already a contiguous (n, T, 2) float64 device
+    tensor is copied first; a captured call that is to follow in-place updates of the plan must
+    be given that form, so that the kernel reads the caller's tensor.
+    Returns RiskAudit; enqueues two launches on the current stream, never synchronises."""
+    lib = _lib.load()
+    dev = store.device
+    C = store.n_cells
+    T = store.T if T is None else int(T)
+    if not 1 <= T <= store.T:
+        raise ValueError(f"T = {T} outside [1, {store.T}] (the store's horizon)")
+    if plan is None and rec is None:
+        raise ValueError("risk_audit needs a plan, records, or both")
+    if getattr(store, "offsets", None) and any(int(o) % 4 for o in store.offsets):
+        raise ValueError("cell offsets must be multiples of 4 particles")
+    t_plan = None
+    if plan is not None:
+        t_plan = torch.as_tensor(plan, device=dev)
+        if t_plan.dim() == 2:
+            t_plan = t_plan.unsqueeze(0)
+        if t_plan.dim() != 3 or t_plan.shape[1] < T or t_plan.shape[2] < 2:
+            raise ValueError(f"plan must be (T, >= 2) or (n_plans, T, >= 2) with T >= {T}")
+        if (t_plan.dtype != torch.float64 or tuple(t_plan.shape[1:]) != (T, 2)
+                or not t_plan.is_contiguous()):
+            t_plan = t_plan[:, :T, :2].to(torch.float64).contiguous()
+        n_plans = int(t_plan.shape[0])
+        if cell_plan is None:
+            if n_plans != 1:
+                raise ValueError(f"{n_plans} plans need cell_plan")
+        elif torch.is_tensor(cell_plan):    # device-resident: its range is the caller's contract
+            if (cell_plan.dtype != torch.int32 or tuple(cell_plan.shape) != (C,)
+                    or cell_plan.device != dev or not cell_plan.is_contiguous()):
+                raise ValueError(f"cell_plan must be a contiguous int32 [{C}] tensor on {dev}")
+        else:
+            host = np.asarray(cell_plan, np.int64).reshape(-1)
+            if host.shape[0] != C or (C and (host.min() < 0 or host.max() >= n_plans)):
+                raise ValueError(f"cell_plan must hold {C} indices in [0, {n_plans})")
+            cell_plan = torch.as_tensor(host.astype(np.int32), device=dev)
+    else:
+        cell_plan = None
+    P = 0
+    if rec is not None:
+        if rec_kind not in (_lib.REC_KIND_HALFSPACE, _lib.REC_KIND_AFFINE,
+                            _lib.REC_KIND_HALFSPACE_COMPACT, _lib.REC_KIND_AFFINE_COMPACT):
+            raise ValueError(f"unknown rec_kind {rec_kind!r}")
+        P = _audit_rows(rec_kind, T)
+        width = 32 if rec_kind >= _lib.REC_KIND_HALFSPACE_COMPACT else 128
+        if rec.dtype != torch.uint8:
+            rec = rec.view(torch.uint8)
+        rec = rec.reshape(C, -1, width) if rec.dim() != 3 else rec
+        if rec.shape[0] != C or rec.shape[2] != width or rec.shape[1] < P:
+            raise ValueError(f"rec must be ({C}, >= {P}, {width}) bytes for rec_kind {rec_kind}")
+        if P == 0:
+            pass                        # T = 1 half-space kinds: no rows, only out_open
+        elif rec.shape[1] != P:         # rows of a longer horizon's buffer
+            rec = rec[:, :P].contiguous()
+        elif not rec.is_contiguous():
+            rec = rec.contiguous()
+    if out is None:
+        i64 = dict(dtype=torch.int64, device=dev)
+        out = RiskAudit(
+            torch.empty((C, T), **i64) if plan is not None else None,
+            torch.empty((C,), **i64) if plan is not None else None,
+            torch.empty((C, T), dtype=torch.float64, device=dev) if plan is not None else None,
+            torch.empty((C, P), **i64) if rec is not None else None,
+            torch.empty((C, T), **i64) if rec is not None else None)
+    else:
+        want = dict(hit=(C, T), hit_any=(C,), min_d2=(C, T), rec_open=(C, P), open=(C, T))
+        for name, shape in want.items():
+            t = getattr(out, name)
+            on = (plan is not None) if name in ("hit", "hit_any", "min_d2") else (rec is not None)
+            if on and (t is None or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"out.{name} must be a contiguous {shape} tensor")
+    on_p, on_r = plan is not None, rec is not None
+    if C == 0:
+        return out
+    _lib.check(lib.ccmpc_risk_audit(
+        _p(store.pos), store.ccmpc_dtype, store.ld, T, _p(store.origin), _p(store.cell_off),
+        _p(store.cell_cnt), C, store.n_bound, _p(t_plan), _p(cell_plan),
+        # no rows (T = 1 half-space kinds): any non-null address switches the record half on
+        (_p(rec) if P else _p(store.pos)) if on_r else None, int(rec_kind) if on_r else 0,
+        float(R),
+        _p(out.hit if on_p else None), _p(out.hit_any if on_p else None),
+        _p(out.min_d2 if on_p else None), _p(out.rec_open if on_r else None),
+        _p(out.open if on_r else None), _stream()), "ccmpc_risk_audit")
+    return out
 
 
 def bucket(z, sample_store, latent_pmf, minpos, filter_pmf=0.1, max_k=None):

@@ -486,6 +486,7 @@ class MidlevelAgent:
         self.prob_lower_save = None
         self.last_records = None
         self._last_rec = None              # (device records, kind, T) of the last generator
+        self._audit_src = None             # (scene, K, T, _last_rec or None) of the last graph step
         self._last_sbig = False            # do its rows carry S_big (road boundaries)?
         self._qp_request = None            # the frame's QP inputs, set before its step graph
         self._qp_pending = None            # ((run, gen), records, (T, u_order)) enqueued
@@ -915,6 +916,7 @@ class MidlevelAgent:
         h = engine.halfspaces(rec)[:, :T * (T - 1) // 2]     # T = 1 keeps one unused slot
         self.last_records = h
         self._last_rec = (rec, mpc.REC_HALFSPACE, T)
+        self._audit_src = None
         self._last_sbig = False             # the Minkowski rows carry no S_big (:926-939)
         constraints = self._records_to_halfspaces(h, scene, T)
         pl_h = pl.cpu().numpy()
@@ -945,6 +947,7 @@ class MidlevelAgent:
         h = engine.affine_records(rec)
         self.last_records = h
         self._last_rec = (rec, mpc.REC_AFFINE, T)
+        self._audit_src = None
         self._last_sbig = True              # + S_big_repeated[0, t] on both sides (:1503-1515)
         cons = []
         for c, (o, k) in enumerate(scene.cell_of):
@@ -1009,6 +1012,7 @@ class MidlevelAgent:
         h = engine.affine_records(rec)
         self.last_records = h
         self._last_rec = (rec, mpc.REC_AFFINE, T)
+        self._audit_src = None
         # the scale-ideal rows carry + S_big_repeated[0, t] (:2394-2414), the robust ones
         # do not (:1828-1849)
         self._last_sbig = bool(scaled)
@@ -1086,6 +1090,8 @@ class MidlevelAgent:
         constraints = HalfSpaceList(h, scene.cell_of, P)
         self.last_records = h[:, :P]
         self._last_rec = (g.out.d("rec"), mpc.REC_HALFSPACE, T)
+        # audit_plan: the records were generated from the sampled store only at T == ph
+        self._audit_src = (scene, list(K), T, self._last_rec if T == ph else None)
         self._last_sbig = False
         return ovs, self._step_tuple(g, o, scene, K, 0, constraints=constraints)
 
@@ -1103,6 +1109,7 @@ class MidlevelAgent:
         h = o["records"]
         self.last_records = h
         self._last_rec = (g.out.d("rec"), mpc.REC_AFFINE, T)
+        self._audit_src = (scene, list(K), T, self._last_rec)
         self._last_sbig = True
         st = h["status"]
         if st.any():
@@ -1377,6 +1384,30 @@ class MidlevelAgent:
             run, gen = self._qp_launch(x_init, goal, ref_traj, T, rec, kind, u_prev, lon,
                                        u_order)
         return self._qp_result(run.wait(gen), goal)
+
+    def audit_plan(self, X_star, R=None):
+        """Monte-Carlo audit of a plan on the sampled scene of the last predict_and_constrain /
+        predict_and_constrain_affine frame (engine.risk_audit on the step graph's bucketed
+        store, its first Tsh planes): how many particles of each cell X_star (Tsh, >= 2; the
+        QP's X_star) passes within R (default: the agent's) of.  At Tsh == ph, where the frame's
+        records were generated from that store, the records are audited too; below ph they come
+        from the ideal rollout, which is never materialised, so the record half is None.
+        Like the OVehicles' device-backed fields, the store must be read before the next step
+        of the same shape (raises after it).  Never called implicitly; returns
+        risk.audit_report's dict and changes no planner state."""
+        if self._audit_src is None:
+            raise RuntimeError("no sampled scene: call predict_and_constrain or "
+                               "predict_and_constrain_affine first")
+        scene, K, T, last = self._audit_src
+        scene.check_live()
+        X = np.asarray(X_star, np.float64)
+        if X.ndim != 2 or X.shape[0] != T or X.shape[1] < 2:
+            raise ValueError(f"X_star must be ({T}, >= 2) for the last frame's Tsh = {T}")
+        plan = torch.as_tensor(np.ascontiguousarray(X[None, :, :2]), device=self.device)
+        rec, kind = (last[0], last[1]) if last is not None else (None, None)
+        a = engine.risk_audit(scene.store, plan=plan, rec=rec, rec_kind=kind,
+                              R=self.R if R is None else float(R), T=T)
+        return risk.audit_report(a, scene.store.counts, K, self.prediction_horizon)
 
     def _qp_launch(self, x_init, goal, ref_traj, T, rec, kind, u_prev, lon, u_order):
         """Enqueue solve_planning_qp's device work on the current stream (no wait): the LTV

@@ -57,3 +57,54 @@ def scenes_cell_risk(scene_K, ph, target_p=TARGET_P):
 def cell_gamma(eps_ura_mat, K, ph):
     """(n_cells,) = norm.ppf(1 - eps_ura[ov, k] / ph) for the GMM-affine generator."""
     return cell_risk(eps_ura_mat, K, ph)[:, 2].copy()
+
+
+def _np(x):
+    if x is None:
+        return None
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def audit_report(audit, counts, K, ph, eps=EPS_TOTAL):
+    """Host-side report of an engine.RiskAudit (device tensors or arrays) against the risk
+    budget: counts [n_cells] particles per cell, K modes per OV (cells in (ov, k) order), ph the
+    horizon the per-step budget is split over.  Reports only: raises nothing about the risk and
+    changes no planner decision.  Returns a dict of NumPy arrays --
+      p_hit [C, T], p_hit_any [C], p_open [C, T]  counts over N_c (nan for an empty cell; None
+                                                  for a half the audit did not run)
+      min_dist [C, T]                             sqrt(min_d2)
+      hit, hit_any, open, min_d2, rec_open        the audit's own arrays (rec_open -1: record
+                                                  not audited), counts [C] = N_c
+      budget_traj [C] = eps_ura[o, k], budget_step [C] = eps_ura[o, k] / ph
+      traj_within_budget [C]    p_hit_any <= budget_traj   (False for an empty cell's nan)
+      step_within_budget [C, T] p_hit <= budget_step
+      worst (cell, t)           the step with the largest p_hit (None without a plan or
+                                without particles), worst_p_hit its value."""
+    K = [int(k) for k in K]
+    n = np.asarray(counts, np.float64).reshape(-1)
+    if n.shape[0] != sum(K):
+        raise ValueError(f"{n.shape[0]} cell counts for {sum(K)} cells")
+    e = eps_ura(K, eps)
+    budget_traj = np.array([e[o, k] for o, k_o in enumerate(K) for k in range(k_o)], np.float64)
+    budget_step = budget_traj / ph
+    hit, hit_any, min_d2 = _np(audit.hit), _np(audit.hit_any), _np(audit.min_d2)
+    rec_open, opn = _np(audit.rec_open), _np(audit.open)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = np.where(n > 0, n, np.nan)
+        p_hit = None if hit is None else hit / den[:, None]
+        p_hit_any = None if hit_any is None else hit_any / den
+        p_open = None if opn is None else opn / den[:, None]
+        min_dist = None if min_d2 is None else np.sqrt(min_d2)
+    out = dict(p_hit=p_hit, p_hit_any=p_hit_any, p_open=p_open, min_dist=min_dist,
+               hit=hit, hit_any=hit_any, open=opn, min_d2=min_d2, counts=n.astype(np.int64),
+               rec_open=rec_open, budget_traj=budget_traj, budget_step=budget_step,
+               traj_within_budget=None, step_within_budget=None, worst=None, worst_p_hit=None)
+    if p_hit is not None:
+        with np.errstate(invalid="ignore"):
+            out["traj_within_budget"] = p_hit_any <= budget_traj
+            out["step_within_budget"] = p_hit <= budget_step[:, None]
+        if p_hit.size and not np.all(np.isnan(p_hit)):
+            c, t = np.unravel_index(int(np.nanargmax(p_hit)), p_hit.shape)
+            out["worst"] = (int(c), int(t))
+            out["worst_p_hit"] = float(p_hit[c, t])
+    return out

@@ -1,6 +1,7 @@
 // Error plumbing and version entry points of the C ABI (include/ccmpc.h).
 #include <string>
 
+#include "audit.hpp"
 #include "ccmpc_common.hpp"
 
 namespace ccmpc {
@@ -222,6 +223,53 @@ extern "C" int ccmpc_compact_records(const void *rec, int rec_kind, int64_t n_re
                      ccmpc::as_stream(stream), static_cast<const unsigned char *>(rec),
                      rec_kind == CCMPC_REC_KIND_AFFINE ? 1 : 0, n_rec,
                      reinterpret_cast<double4 *>(out));
+  CCMPC_LAUNCH_CHECK();
+  return CCMPC_OK;
+}
+
+// ---- Monte-Carlo risk audit (audit.hip) -----------------------------------------------------
+extern "C" int ccmpc_risk_audit(const void *positions, int dtype, int64_t ld, int64_t T,
+                                const double *origin, const int64_t *cell_off,
+                                const int64_t *cell_cnt, int64_t n_cells,
+                                int64_t n_particles_bound, const double *plan,
+                                const int32_t *cell_plan, const void *rec, int rec_kind, double R,
+                                int64_t *out_hit, int64_t *out_hit_any, double *out_min_d2,
+                                int64_t *out_rec_open, int64_t *out_open,
+                                ccmpc_stream_t stream) {
+  CCMPC_REQUIRE(T >= 1 && T <= ccmpc::kAuditMaxT, "T must be in [1, 40]");
+  CCMPC_REQUIRE(std::isfinite(R) && R > 0.0, "R must be finite and positive");
+  CCMPC_REQUIRE(plan || rec, "nothing to audit: plan and rec are both null");
+  int P = 0;
+  if (rec) {
+    P = ccmpc::audit_rows(rec_kind, T);
+    CCMPC_REQUIRE(P >= 0, "unknown rec_kind");
+    // P == 0 (T = 1 of the half-space kinds): out_rec_open has no rows and may be null
+    CCMPC_REQUIRE((out_rec_open || P == 0) && out_open,
+                  "record half needs out_rec_open and out_open");
+    CCMPC_REQUIRE(ccmpc::aligned(rec, 16), "records must be 16-byte aligned");
+  }
+  if (plan) {
+    CCMPC_REQUIRE(out_hit && out_hit_any && out_min_d2,
+                  "plan half needs out_hit, out_hit_any and out_min_d2");
+    CCMPC_REQUIRE(ccmpc::aligned(plan, 8), "plan must be 8-byte aligned");
+  }
+  CCMPC_REQUIRE(n_cells >= 0 && n_cells < (1 << 30), "bad n_cells");
+  CCMPC_REQUIRE(n_particles_bound >= 0, "bad n_particles_bound");
+  CCMPC_REQUIRE(dtype == CCMPC_F64 || dtype == CCMPC_F32, "bad dtype");
+  CCMPC_REQUIRE(ld % 4 == 0 && ld > 0, "ld must be a positive multiple of 4");
+  if (n_cells == 0) return CCMPC_OK;
+  CCMPC_REQUIRE(positions && cell_off && cell_cnt, "null pointer");
+  CCMPC_REQUIRE(ccmpc::aligned(positions, 16), "positions must be 16-byte aligned");
+  CCMPC_REQUIRE(ccmpc::aligned(out_hit, 8) && ccmpc::aligned(out_hit_any, 8) &&
+                    ccmpc::aligned(out_min_d2, 8) && ccmpc::aligned(out_rec_open, 8) &&
+                    ccmpc::aligned(out_open, 8),
+                "outputs must be 8-byte aligned");
+  const ccmpc::AuditArgs a{positions, dtype, ld, static_cast<int>(T), origin, cell_off, cell_cnt,
+                           static_cast<int>(n_cells), n_particles_bound, plan, cell_plan,
+                           static_cast<const unsigned char *>(rec), rec_kind, P, R * R,
+                           out_hit, out_hit_any, out_min_d2, out_rec_open, out_open};
+  const int rc = ccmpc::launch_risk_audit(a, ccmpc::as_stream(stream));
+  CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
   CCMPC_LAUNCH_CHECK();
   return CCMPC_OK;
 }

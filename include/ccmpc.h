@@ -647,6 +647,55 @@ int ccmpc_mpc_qp_ltv(const ccmpc_qp_ltv *ltv, int64_t n_scenes, int64_t T, int64
                      ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Monte-Carlo audit of a plan and of constraint records on the particles they were built from.
+ * No reference counterpart (as ccmpc_compact_records): the reference computes an analytic
+ * lower bound per record and never counts particles; this call gives the empirical number to
+ * set beside it.  One streaming pass over planes 0 .. 2T-1 of the store (T may be smaller than
+ * the horizon the store holds), the bytes ccmpc_moments reads, reduced to integers per cell.
+ * World position of particle i of cell c at step t: the stored pair (F64), or
+ * (double)rel + origin[c] per coordinate (F32; origin NULL = 0).
+ *
+ * Plan half (plan != NULL):
+ *  plan[r][T][2]    ego positions (the first two columns of ccmpc_mpc_qp's out_x), float64
+ *  cell_plan[c]     the plan row cell c is audited against (NULL -> row 0), as cell_ref
+ *  In float64, in this order: dx = px - plan_x, dy = py - plan_y, d2 = dx*dx + dy*dy;
+ *  a particle is hit at step t iff d2 < R*R (strict).
+ *  out_hit[c][T]      particles of cell c hit at step t
+ *  out_hit_any[c]     particles hit at any t < T (the event the per-mode risk budget bounds)
+ *  out_min_d2[c][T]   the smallest d2, +inf for an empty cell
+ *
+ * Record half (rec != NULL): rec[c][P] of rec_kind CCMPC_REC_KIND_HALFSPACE / _AFFINE or their
+ * _COMPACT packing, P = T(T-1)/2 (half-space kinds) or T (affine kinds).  Of a record only
+ * n0, n1, rhs (the half-space record's d, the affine record's rhs, as ccmpc_compact_records),
+ * side, status and its step t (t_tau >> 16 for the half-space kinds, else t / t_tau) are read.
+ * A record protects a particle when the ego may stand anywhere on the record's feasible side
+ * and still be at least R away: with s = n0*px + n1*py and v = side * (rhs - s),
+ *   protected iff v >= 0 && v*v >= (R*R) * (n0*n0 + n1*n1)     (no square root)
+ *  out_rec_open[c][P] particles of the cell the record does not protect at its step; -1 for a
+ *                     record with status != 0 or t outside [0, T): such a record indexes no
+ *                     plane and protects nothing
+ *  out_open[c][T]     particles protected by no status-0 record of (c, t); the whole cell
+ *                     where (c, t) has none (t = 0 of the half-space kinds)
+ * If the plan satisfies every status-0 record of (c, t), every hit particle is open there:
+ * out_hit[c][t] <= out_open[c][t].
+ *
+ * plan == NULL skips the three plan outputs, rec == NULL the two record outputs (those
+ * pointers may then be NULL); both NULL is CCMPC_ERR_ARG, as are T outside [1, 40], R not
+ * finite or <= 0, an unknown rec_kind, ld not a multiple of 4 and a missing output of an
+ * enabled half.  cell_off entries must be multiples of 4, as for ccmpc_moments.
+ * n_particles_bound >= sum(cell_cnt) sizes the grid; counts and offsets are read on the device.
+ * Outputs need no initialisation: the call is two launches (initial values, then the pass),
+ * no workspace.  Counts are integer atomics and min_d2 an unsigned integer minimum on the bit
+ * pattern of the non-negative double, so the result does not depend on execution order.
+ * ------------------------------------------------------------------------------------- */
+int ccmpc_risk_audit(const void *positions, int dtype, int64_t ld, int64_t T,
+                     const double *origin, const int64_t *cell_off, const int64_t *cell_cnt,
+                     int64_t n_cells, int64_t n_particles_bound, const double *plan,
+                     const int32_t *cell_plan, const void *rec, int rec_kind, double R,
+                     int64_t *out_hit, int64_t *out_hit_any, double *out_min_d2,
+                     int64_t *out_rec_open, int64_t *out_open, ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * TEST ONLY (not a reference interface): the half-space tail's device functions -- the ones
  * ccmpc_minkowski_cycle / ccmpc_minkowski / ccmpc_affine_scale run per record -- on n batched
  * inputs, so the reference's component golden vectors reach the device arithmetic.  Device
