@@ -163,14 +163,26 @@ struct PairMoments {
   bool ok;
 };
 
+// The inverse of the diagonal block C_tau,tau with its `ok` flag: it depends on tau alone, so a
+// cell has T of them for its T (T - 1) / 2 pairs.
+struct BlockInverse {
+  M2 inv;
+  bool ok;
+};
+__device__ __forceinline__ BlockInverse block_inverse(const M2 &c_tau) {
+  BlockInverse bi;
+  bi.ok = inv2(c_tau, bi.inv);
+  return bi;
+}
+
 __device__ __forceinline__ PairMoments pair_moments(const double *C, int rows, int t, int tau) {
   PairMoments pm;
+  const BlockInverse bi = block_inverse(block(C, rows, tau, tau));
   pm.c_t = block(C, rows, t, t);
   const M2 c_x = block(C, rows, t, tau);
   const M2 c_xT = block(C, rows, tau, t);
-  M2 inv_tau;
-  pm.ok = inv2(block(C, rows, tau, tau), inv_tau);
-  pm.cov_mu = mul(mul(c_x, inv_tau), c_xT);
+  pm.ok = bi.ok;
+  pm.cov_mu = mul(mul(c_x, bi.inv), c_xT);
   pm.cov_infer = sub(pm.c_t, pm.cov_mu);
   return pm;
 }
@@ -220,21 +232,34 @@ __device__ __forceinline__ int closest_tangent(const M2 &S, double c, double n0,
   return 0;
 }
 
+// The tangent's slope at step t and everything else that depends only on the step's mean
+// (m0, m1) and reference point (a0, a1): the normal n = [n0, 1] = [-m, 1], proj = n.mu,
+// nrm = |n|, na = n.a.  A cell has T of them for its T (T - 1) / 2 pairs.
+struct TangentFrame {
+  double m, n0, proj, nrm, na;
+};
+__device__ __forceinline__ TangentFrame tangent_frame(double m0, double m1, double a0, double a1) {
+  TangentFrame f;
+  f.m = -(a0 - m0) / (a1 - m1);
+  f.n0 = -f.m;
+  const double n1 = 1.0;
+  f.proj = f.n0 * m0 + n1 * m1;
+  f.nrm = sqrt(f.n0 * f.n0 + n1 * n1);
+  f.na = f.n0 * a0 + n1 * a1;
+  return f;
+}
+
 // One (cell, t, tau) record except its lower bound, from the cell's 2T x 2T covariance C (row
 // stride `rows`) and mean mu (v8ideal/__init__.py:893-943), written straight to `out`.
 __device__ void minkowski_pair(const double *C, const double *mu, const double *ref, int rows,
                                int t, int tau, double chi_r, double chi_p, double R, double tol,
                                int maxiter, ccmpc_halfspace *out) {
-  // the tangent's slope and everything that depends only on the mean and the reference
-  // point: computed ahead of the MVOE fixed points (straight-line code the scheduler overlaps
-  // with the pair-moment chain; after the data-dependent loops it would be pure latency)
+  // the tangent frame: computed ahead of the MVOE fixed points (straight-line code the
+  // scheduler overlaps with the pair-moment chain; after the data-dependent loops it would be
+  // pure latency)
   const double m0 = mu[2 * t], m1 = mu[2 * t + 1];
-  const double a0 = ref[2 * t], a1 = ref[2 * t + 1];
-  const double m = -(a0 - m0) / (a1 - m1);
-  const double n0 = -m, n1 = 1.0;
-  const double proj = n0 * m0 + n1 * m1;
-  const double nrm = sqrt(n0 * n0 + n1 * n1);
-  const double na = n0 * a0 + n1 * a1;
+  const TangentFrame f = tangent_frame(m0, m1, ref[2 * t], ref[2 * t + 1]);
+  const double m = f.m, n0 = f.n0, n1 = 1.0, proj = f.proj, nrm = f.nrm, na = f.na;
   // the record goes out in 16-byte pairs (the lower bound at byte 88 belongs to another
   // thread), the fields known early ahead of the chain, so few stores follow its end
   store_pair(&out->n0, n0, n1);
@@ -263,7 +288,7 @@ __device__ void minkowski_pair(const double *C, const double *mu, const double *
     if (ts != 0) {
       if (status == 0) status = ts;
     } else if (isfinite(d)) {
-      side = (n0 * m0 + n1 * m1 <= d) ? 1 : -1;  // (:926) n.mean <= d  ->  n.x >= d
+      side = (proj <= d) ? 1 : -1;  // (:926) n.mean <= d  ->  n.x >= d
     }
   }
   if (status == 0 && !(isfinite(d) && isfinite(Q.a) && isfinite(QR.a) && isfinite(m0)))

@@ -690,17 +690,24 @@ inline bool tree_layout(void *ws, size_t ws_bytes, int64_t max_items, int64_t n_
 }
 
 
-// Sum the entry pair (e, e+1), e even, over n <= kFanIn consecutive slabs: all 16-byte sc1 loads
-// issued first (indices clamped, no per-load branch), then a fixed-order sum.
+// Sum the entry pair (e, e+1), e even, over n <= kFanIn consecutive slabs (n >= 1; slab0 and n are
+// wave-uniform in the cycle kernels -- in root_finalize_kernel, whose thread-to-slab map does not
+// follow wave boundaries, they differ within a wave and the compiler loops over the distinct
+// descriptors, size included):
+// all kFanIn 16-byte sc1 loads issued first, no per-load branch, then a fixed-order sum.  A
+// gather's time goes with the loads that reach memory, not with its round trips (phase stamps,
+// profiles/r08): clamping the index of the loads past slab n - 1 re-read that slab up to 15
+// times, and a 7-slab root took as long as a 16-slab one.  They are now cut off by the buffer
+// descriptor's size instead: C2 cycle 10.26 -> 10.03 us (profiles/r08/ab/variants_headline.log).
 __device__ __forceinline__ double2 sum_group2(const double *__restrict__ slab0, int64_t n, int E,
                                               int e) {
-  const __amdgpu_buffer_rsrc_t rs = slab_rsrc(slab0);
   double2 v[kFanIn];
+  // the descriptor ends with slab n - 1, so the loads of slabs i >= n are out of range: the
+  // buffer unit answers them with zeros and sends nothing to memory
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<double *>(slab0), 0, static_cast<int>(n) * E * 8, 0x00020000);
 #pragma unroll
-  for (int i = 0; i < kFanIn; ++i) {
-    const int j = static_cast<int>(i < n ? i : n - 1);
-    v[i] = ld2_sc1(rs, 8 * (j * E + e));
-  }
+  for (int i = 0; i < kFanIn; ++i) v[i] = ld2_sc1(rs, 8 * (i * E + e));
   double2 s = v[0];
 #pragma unroll
   for (int i = 1; i < kFanIn; ++i) {
@@ -753,6 +760,19 @@ struct Scheme16 {
   static constexpr int D = 16 * RB;
   static constexpr int E = GRAM + D;
   __device__ static void decode(int e, int &i, int &j) { decode_entry(e, RB, i, j); }
+  // Row-sum pair r = 8 b + l (rows 16 b + 2 l, + 1) rides in the slot of the entry pair
+  // (lane l < 8, registers 2 and 3) of diagonal tile (b, b): rows 16 b + 8 and + 12, column
+  // 16 b + l -- below the diagonal, so no finaliser ever uses it.  -1: e hosts nothing.
+  __device__ static int hosted_row_pair(int e) {
+    const int l = (e >> 2) & 63;
+    if ((e & 3) != 2 || l >= 8) return -1;
+    int bi = 0, t = e >> 8;
+    while (t >= RB - bi) {
+      t -= RB - bi;
+      ++bi;
+    }
+    return t == 0 ? 8 * bi + l : -1;
+  }
 };
 
 __host__ __device__ constexpr int n_pairs(int nb) { return nb * (nb + 1) / 2; }
@@ -771,6 +791,18 @@ struct Scheme4 {
     }
     i = 4 * I + ((e >> 2) & 3);
     j = 4 * (I + p) + (e & 3);
+  }
+  // Row-sum pair r = 2 I + h (rows 4 I + 2 h, + 1) rides in the slot of the entry pair (row
+  // 2 + h, columns 0 and 1) of diagonal block (I, I): below the diagonal, never used.
+  __device__ static int hosted_row_pair(int e) {
+    const int i = (e >> 2) & 3;
+    if ((e & 3) != 0 || i < 2) return -1;
+    int p = e >> 4, I = 0;
+    while (p >= NB - I) {
+      p -= NB - I;
+      ++I;
+    }
+    return p == 0 ? 2 * I + (i - 2) : -1;
   }
 };
 
@@ -852,20 +884,111 @@ __device__ __forceinline__ void combine4(const double (&acc)[n_pairs(NB)], const
   __syncthreads();
 }
 
-// The last arriver's root combine: every summed entry pair of the n <= 16 root slabs into LDS
-// in ONE round of 16-byte sc1 loads (the finaliser then reads LDS only, instead of paying a
-// second dependent global round trip for the Gram tiles after the row sums).  Ends with a
-// barrier.
-template <int E>
+// Which Gram positions the entry pair (e, e+1), e even and < GRAM, holds, and which of the two
+// the finaliser uses: one value per symmetric pair inside the live rows.  finalize_cell and
+// gather_root's spread path share it, so what that path gathers is exactly what is read.
+struct PairUse {
+  int i0, j0, i1, j1;
+  bool use0, use1;
+};
+template <typename Sch>
+__device__ __forceinline__ PairUse pair_use(int e, int rows) {
+  PairUse u;
+  Sch::decode(e, u.i0, u.j0);
+  Sch::decode(e + 1, u.i1, u.j1);
+  u.use0 = u.i0 < rows && u.j0 < rows && u.i0 <= u.j0;
+  u.use1 = u.i1 < rows && u.j1 < rows && u.i1 <= u.j1;
+  return u;
+}
+
+// Slot p in [0, GRAM / 2) of a root gather -> the entry pair it fetches, or -1 for none: the
+// Gram pair (2p, 2p + 1) when the finaliser uses it; else, where that pair is one of the
+// scheme's never-used hosts (hosted_row_pair), the row-sum pair it hosts.  So GRAM / 2 slots
+// cover all E / 2 pairs a cell needs, and at T <= 8 two groups' slots are exactly one 256-thread
+// workgroup.
+template <typename Sch>
+__device__ __forceinline__ int gather_entry(int p, int rows) {
+  const PairUse u = pair_use<Sch>(2 * p, rows);
+  if (u.use0 || u.use1) return 2 * p;
+  const int r = Sch::hosted_row_pair(2 * p);
+  return r >= 0 ? Sch::GRAM + 2 * r : -1;
+}
+
+// LDS doubles gather_root needs beside its destination: one slab per further group of a root.
+__host__ __device__ constexpr int gather_part_doubles(int E) {
+  return (CCMPC_ROOT_FANIN / kFanIn - 1) * E;
+}
+
+// The last arriver's root combine: the summed entry pairs of the root's n <= kRootFanIn slabs
+// into LDS (the finaliser then reads LDS only, instead of paying a second dependent global
+// round trip for the Gram tiles after the row sums).
+//  * n <= kFanIn: every thread sums its pairs over the slabs (sum_group2): one round of 16-byte
+//    sc1 loads per pair a thread holds, every pair of the slab.  (Skipping the pairs the
+//    finaliser does not use was built and measured here too: the predicate in front of the
+//    loads cost a T = 8 cell 0.1 us and the 4-row-block C4 batch with the f32 store 0.4 us --
+//    27.65 without, 28.18 with, parent 27.71, profiles/r08/ab/c4_f32_mask.log -- for bytes that
+//    a gather's time does not go with.)
+//  * n > kFanIn: the groups of kFanIn slabs go to different threads -- thread s takes slot
+//    s % HP of group s / HP (gather_entry; HP = GRAM / 2 padded to whole waves, so a wave never
+//    straddles two groups) -- so a thread never has more than one
+//    group's loads in its registers, and every load of a pass is in flight before the first add
+//    that needs one.  Group 0 lands in dst_lds, group q > 0 in part_lds + (q - 1) E
+//    (gather_part_doubles(E) doubles); after a barrier the groups are added in index order,
+//    ((G0 + G1) + G2) + G3, each group sum being sum_group2's left-to-right chain: the bits of a
+//    group-by-group gather.  Only the pairs finalize_cell uses are loaded and written here --
+//    the Gram pairs with a position on or above the diagonal inside the 2T live rows
+//    (pair_use), and every row-sum pair -- which is what lets two groups' slots fit one
+//    workgroup; the rest of dst_lds is left as it was and must not be read.  Passes: ceil(groups HP / threads) -- with 256 threads, at T <= 10
+//    (HP = 128) one for <= 32 slabs and two for <= 64; wider Grams take more slots than threads
+//    and proportionally more passes, never more than the per-thread group loop took.
+// The branch on root_n is workgroup-uniform.  Ends with a barrier.
+template <typename Sch>
 __device__ __forceinline__ void gather_root(const double *__restrict__ root, int32_t root_n,
-                                            double *dst_lds) {
-  for (int e = 2 * threadIdx.x; e < E; e += 2 * blockDim.x) {
-    double2 s = sum_group2(root, min(root_n, kFanIn), E, e);
-    for (int k = kFanIn; k < root_n; k += kFanIn) {  // fixed order: deterministic
-      const double2 t = sum_group2(root + static_cast<int64_t>(k) * E, min(root_n - k, kFanIn),
-                                   E, e);
-      s.x += t.x;
-      s.y += t.y;
+                                            int rows, double *dst_lds, double *part_lds) {
+  constexpr int E = Sch::E, GRAM = Sch::GRAM, H = Sch::GRAM / 2;
+  constexpr int HP = (H + 63) / 64 * 64;  // a group's slots, padded to whole waves
+  const int tid = threadIdx.x, nth = blockDim.x;
+  if (root_n <= kFanIn || root_n > kRootFanIn || !part_lds) {
+    // (a root wider than kRootFanIn exists only at the tree's depth bound; it, and a caller
+    // with no LDS for the groups, passing part_lds = nullptr, go group by group in each thread)
+    for (int e = 2 * tid; e < E; e += 2 * nth) {
+      double2 s = sum_group2(root, min(root_n, kFanIn), E, e);
+      for (int k = kFanIn; k < root_n; k += kFanIn) {  // fixed order: deterministic
+        const double2 t = sum_group2(root + static_cast<int64_t>(k) * E, min(root_n - k, kFanIn),
+                                     E, e);
+        s.x += t.x;
+        s.y += t.y;
+      }
+      dst_lds[e] = s.x;
+      dst_lds[e + 1] = s.y;
+    }
+    __syncthreads();
+    return;
+  }
+  const int ng = (root_n + kFanIn - 1) >> kLgFanIn;
+  for (int s = tid; s < ng * HP; s += nth) {
+    // a wave's 64 slots are in one group (HP and the workgroup are whole waves), so the group's
+    // base and slab count stay in scalar registers, as in the one-group path
+    const int q = __builtin_amdgcn_readfirstlane(s / HP);
+    const int p = s - q * HP;
+    const int e = p < H ? gather_entry<Sch>(p, rows) : -1;
+    if (e < 0) continue;
+    const double2 g = sum_group2(root + static_cast<int64_t>(q * kFanIn) * E,
+                                 min(root_n - q * kFanIn, kFanIn), E, e);
+    double *d = q ? part_lds + (q - 1) * E : dst_lds;
+    d[e] = g.x;
+    d[e + 1] = g.y;
+  }
+  __syncthreads();
+  for (int e = 2 * tid; e < E; e += 2 * nth) {
+    if (e < GRAM) {
+      const PairUse u = pair_use<Sch>(e, rows);
+      if (!u.use0 && !u.use1) continue;
+    }
+    double2 s = {dst_lds[e], dst_lds[e + 1]};
+    for (int q = 1; q < ng; ++q) {  // fixed order: deterministic
+      s.x += part_lds[(q - 1) * E + e];
+      s.y += part_lds[(q - 1) * E + e + 1];
     }
     dst_lds[e] = s.x;
     dst_lds[e + 1] = s.y;
@@ -906,17 +1029,13 @@ __device__ void finalize_cell(Reader rd, int64_t cnt, int T, const double *shift
     if (mean_lds) mean_lds[r] = m;
   }
   for (int e = 2 * tid; e < GRAM; e += 2 * nth) {
-    int i0, j0, i1, j1;
-    Sch::decode(e, i0, j0);
-    Sch::decode(e + 1, i1, j1);
-    const bool use0 = i0 < rows && j0 < rows && i0 <= j0;  // one value per symmetric pair
-    const bool use1 = i1 < rows && j1 < rows && i1 <= j1;
-    if (!use0 && !use1) continue;
+    const PairUse u = pair_use<Sch>(e, rows);  // one value per symmetric pair
+    if (!u.use0 && !u.use1) continue;
     const double2 g = rd(e);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      if (!(h ? use1 : use0)) continue;
-      const int i = h ? i1 : i0, j = h ? j1 : j0;
+      if (!(h ? u.use1 : u.use0)) continue;
+      const int i = h ? u.i1 : u.i0, j = h ? u.j1 : u.j0;
       const double c = ((h ? g.y : g.x) - S[i] * S[j] / n) / (n - 1.0);
       cov[i * rows + j] = c;
       cov[j * rows + i] = c;

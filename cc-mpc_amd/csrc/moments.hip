@@ -284,7 +284,7 @@ __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &lo
                                     &root_n);
     PROBE_TS(4);
     if (!last) return;
-    gather_root<E>(root, root_n, L.slab);
+    gather_root<Sch>(root, root_n, rows, L.slab, L.cov);  // the exchange buffer is free here
     PROBE_GATHERED();
   }
   finalize_cell<Sch>([&](int e) { return double2{L.slab[e], L.slab[e + 1]}; }, loc.cnt, T,
@@ -353,6 +353,7 @@ void moments_kernel(
   constexpr bool DEFER = defer_root(RB, MINK, BAL);
   constexpr int XCH = combine_xch_doubles(RB, G::NW) > (MINK ? D * D : 0)
                           ? combine_xch_doubles(RB, G::NW) : D * D;
+  static_assert(XCH >= gather_part_doubles(E), "xch must hold the root gather's group slabs");
   __shared__ double xch[XCH];
   __shared__ double slab_lds[E];
   __shared__ double shift_lds[D];
@@ -703,6 +704,8 @@ __global__ __launch_bounds__(kNW4 * 64, m4_occ<P>(NB)) void moments4_kernel(
       if (w == 0 && m == 0) shift_lds[4 * I + c] = sh[I];
     // the covariance for the tail reuses the exchange buffer (free after combine4)
     static_assert(kNW4 * Combine4Layout<NB>::XS >= D * D, "xch must hold the covariance");
+    static_assert(kNW4 * Combine4Layout<NB>::XS >= gather_part_doubles(E),
+                  "xch must hold the root gather's group slabs");
     const EpilogueLds L{slab_lds, shift_lds, S_lds, mean_lds, xch, lb_s, ref_lds, &flag};
     cell_epilogue<Sch, MINK, MINK, false>(
         [&](double *dst, bool to_lds) { combine4<NB, kNW4>(acc, s1, xch, dst, to_lds); }, loc,

@@ -292,7 +292,10 @@ __global__ __launch_bounds__(64 * ideal_waves(RB)) void ideal_gram_kernel(
   double *mean = out_mean + static_cast<int64_t>(cell) * rows;
   double *cov = out_cov + static_cast<int64_t>(cell) * rows * rows;
   static_assert(NW * D * kStageStride >= E, "root staging reuses the sample stage");
-  gather_root<E>(root, root_n, stage_all);  // the sample stage is free after combine_waves
+  // the sample stage is free after combine_waves: the root slab, then (where they fit: T <= 24)
+  // the gather's group slabs
+  constexpr bool kParts = NW * D * kStageStride >= E + gather_part_doubles(E);
+  gather_root<Scheme16<RB>>(root, root_n, rows, stage_all, kParts ? stage_all + E : nullptr);
   finalize_cell<Scheme16<RB>>([&](int e) { return double2{stage_all[e], stage_all[e + 1]}; }, n, T,
                     shift_s, S_lds, 0.0, 0.0, mean, cov, mean_lds, nullptr);
   if (MINK) minkowski_cell(cov, mean_lds, T, cell, mp, lb_s, threadIdx.x, blockDim.x);

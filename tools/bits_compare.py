@@ -20,7 +20,8 @@ CONFIGS = [("C2", 4, 5000, 8, 1, "f32"), ("C3-1e3", 1, 1000, 8, 1, "f32"),
            ("C3-2e4", 1, 20000, 8, 1, "f32"), ("C3-1e5", 1, 100000, 8, 1, "f32"),
            ("C3-2e5", 1, 200000, 8, 1, "f32"), ("C3-1e5-f64", 1, 100000, 8, 1, "f64"),
            ("T12-1e5", 1, 100000, 12, 1, "f32"), ("T20-1e5", 1, 100000, 20, 1, "f32"),
-           ("C4/8", 4, 20000, 12, 8, "f32"), ("C5", 8, 50000, 40, 1, "f32")]
+           ("C4/8", 4, 20000, 12, 8, "f32"), ("C4/8-f64", 4, 20000, 12, 8, "f64"),
+           ("C5", 8, 50000, 40, 1, "f32")]
 
 
 def dump(out):
