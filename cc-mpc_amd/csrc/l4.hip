@@ -309,13 +309,23 @@ __device__ __forceinline__ void support_rows(double theta, double (&A)[4][2]) {
 }
 
 // A particle's step delta and the cos / sin of its heading without the atan2: (dx, dy) times
-// 1 / |(dx, dy)| from the hardware rsqrt with one Newton step (within 2 ulp of cos / sin of the
-// rounded atan2); a zero step keeps sincos of atan2, whose signed-zero cases the ratio cannot
-// express
+// 1 / |(dx, dy)| from the hardware rsqrt with two Newton steps.  Against the exact unit vector
+// d / |d| the error is at most 2.25 x 2^-52 relative by the roundings (n2: 1, halved by the
+// inverse square root; the last Newton update: 1.25; the product: 0.5); measured 1.5, and
+// tests/test_gpu_l4_edges.py enforces 4.  One step is not enough: the MI355X's seed left up to
+// 17 x 2^-52 after it.  Where n2 would be subnormal or underflow (|d| < 2^-480) the delta is
+// first scaled by 2^600, which is exact.  A zero step, or an n2 that overflows, keeps sincos of
+// atan2: the ratio cannot express atan2's signed-zero cases
 __device__ __forceinline__ void heading_cs_rsq(double dx, double dy, double &S, double &C) {
-  const double n2 = dx * dx + dy * dy;
+  double n2 = dx * dx + dy * dy;
+  if (n2 < 0x1p-960) {  // n2 would lose bits (or all of them): |d| < 2^-480 times 2^600, exact
+    dx *= 0x1p600;
+    dy *= 0x1p600;
+    n2 = dx * dx + dy * dy;
+  }
   if (n2 > 0.0 && n2 < INFINITY) {
     double r = __builtin_amdgcn_rsq(n2);
+    r = r * fma(-0.5 * n2 * r, r, 1.5);
     r = r * fma(-0.5 * n2 * r, r, 1.5);
     C = dx * r;
     S = dy * r;
