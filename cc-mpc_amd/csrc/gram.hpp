@@ -582,11 +582,17 @@ __device__ __forceinline__ void combine_waves(const d4 (&acc)[NACC][n_tiles(RB)]
   }
 }
 
+#ifndef PROBE_DRAINED  // diagnostic builds of moments.hip stamp the drain's end in arrive_last
+#define PROBE_DRAINED() \
+  do {                  \
+  } while (0)
+#endif
 // Drain the workgroup's slab stores, take a ticket; true (in every thread) for the last of
 // `nit` arrivals, which also resets the counter for the next launch.
 __device__ __forceinline__ bool arrive_last(int32_t *counter, int64_t nit, int *flag_lds) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains
   __syncthreads();
+  PROBE_DRAINED();
   if (threadIdx.x == 0) {
     const int ticket =
         __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -636,10 +642,28 @@ inline int64_t level_capacity(int64_t max_items, int64_t n_cells, int l) {
   return c + 1;
 }
 
+// Arrival counters sit kCounterStride int32 words apart (build-time knob; 1 = packed).  Packed,
+// a launch's counters share a cache line or two -- C2's nine are words 0..13 -- and every item
+// of the launch sends its returning add to that line within a fraction of a microsecond: the
+// last arriver's add then took 0.82 us to return, against 0.44 us with a 128-byte line per
+// counter (phase stamps, profiles/r09), and the C2 cycle 10.01 -> 9.60 us.  32, 64 and 128 words
+// measure alike (9.63 / 9.60 / 9.63), so the smallest is taken.
+#ifndef CCMPC_CTR_STRIDE
+#define CCMPC_CTR_STRIDE 32
+#endif
+constexpr int kCounterStride = CCMPC_CTR_STRIDE;
+static_assert(kCounterStride >= 1 && kCounterStride <= 128, "counter stride: 1..128 words");
+// The counter region is 1 / kCtrShare of the buffer (ctr_region).  A level holds at most ~1.07
+// counters per node below it and a node is >= 176 doubles, so counters are at most
+// kCounterStride / 320 of the slab bytes: 0.3 % packed, 10 / 20 / 40 % at 32 / 64 / 128 words.
+constexpr size_t kCtrShare =
+    kCounterStride <= 4 ? 32 : (kCounterStride <= 32 ? 8 : (kCounterStride <= 64 ? 4 : 2));
+
 inline size_t tree_counter_bytes(int64_t max_items, int64_t n_cells) {
   size_t ctr = 0;
   for (int l = 0; l < kMaxLevels; ++l)
-    ctr += static_cast<size_t>(level_capacity(max_items, n_cells, l + 1)) * sizeof(int32_t);
+    ctr += static_cast<size_t>(level_capacity(max_items, n_cells, l + 1)) * kCounterStride *
+           sizeof(int32_t);
   return (ctr + kCounterAlign - 1) / kCounterAlign * kCounterAlign;
 }
 
@@ -651,21 +675,25 @@ inline size_t tree_slab_bytes(int64_t max_items, int64_t n_cells, int E) {
 }
 
 // Workspace layout.  The arrival counters live in the first ctr_region(ws_bytes) =
-// round_up(ws_bytes / 32, 256) bytes -- a function of the WHOLE buffer only -- and the slabs
-// after it.  Calls of different shapes sharing one buffer (e.g. a moments call on a small
+// round_up(ws_bytes / kCtrShare, 256) bytes -- a function of the WHOLE buffer only -- and the
+// slabs after it.  Calls of different shapes sharing one buffer (e.g. a moments call on a small
 // store, then a 1e6-sample rollout) therefore agree on where counters are: a per-call
 // counter size would let one call's slabs land on another call's counters, which must be
-// zero when a launch starts (every launch leaves them zero).  Counters are <= 1.7 % of the
-// slab bytes (E >= 176 doubles per node), so 1/32 of the buffer always holds them.
+// zero when a launch starts (every launch leaves them zero).  kCtrShare is sized so that the
+// region always holds the counters (see there); tree_bytes and tree_layout check it anyway.
 inline size_t ctr_region(size_t ws_bytes) {
-  return (ws_bytes / 32 + kCounterAlign - 1) / kCounterAlign * kCounterAlign;
+  return (ws_bytes / kCtrShare + kCounterAlign - 1) / kCounterAlign * kCounterAlign;
 }
 
+// ws - ctr_region(ws) >= s: ctr_region(ws) <= ws / K + 256 and ws >= (c + s) K / (K - 1) - 1 +
+// 512 (K = kCtrShare >= 2), so ws - ctr_region(ws) >= c + s - 1 >= s (c >= 256).  Where the
+// region of that size would not hold the counters (s < (K - 2) c; never at E >= 176), K c is
+// taken instead: its region is exactly c and (K - 1) c > s is left for the slabs.
 inline size_t tree_bytes(int64_t max_items, int64_t n_cells, int E) {
   const size_t c = tree_counter_bytes(max_items, n_cells);
   const size_t s = tree_slab_bytes(max_items, n_cells, E);
-  size_t ws = (c + s) + (c + s) / 31 + 2 * kCounterAlign;  // ws - ctr_region(ws) >= s
-  if (ctr_region(ws) < c) ws = 32 * c;                     // never binds at E >= 176
+  size_t ws = (c + s) + (c + s) / (kCtrShare - 1) + 2 * kCounterAlign;
+  if (ctr_region(ws) < c) ws = kCtrShare * c;
   return (ws + kCounterAlign - 1) / kCounterAlign * kCounterAlign;
 }
 
@@ -678,8 +706,8 @@ inline bool tree_layout(void *ws, size_t ws_bytes, int64_t max_items, int64_t n_
     return false;
   int32_t *c = static_cast<int32_t *>(ws);
   for (int l = 0; l < kMaxLevels; ++l) {
-    L.counters[l] = c;
-    c += level_capacity(max_items, n_cells, l + 1);
+    L.counters[l] = c;  // group g of level l: word g * kCounterStride
+    c += level_capacity(max_items, n_cells, l + 1) * kCounterStride;
   }
   double *s = reinterpret_cast<double *>(static_cast<char *>(ws) + region);
   for (int l = 0; l < kMaxLevels; ++l) {
@@ -729,7 +757,8 @@ __device__ bool tree_climb(const TreeLayout &L, int32_t idx, int32_t nit, int32_
     const bool is_root = n_l <= kRootFanIn || l + 1 == kMaxLevels;
     const int32_t grp = is_root ? 0 : idx >> kLgFanIn;
     const int32_t gsize = is_root ? n_l : min(n_l - grp * kFanIn, kFanIn);
-    if (!arrive_last(L.counters[l] + first_up + grp, gsize, flag)) return false;
+    int32_t *ctr = L.counters[l] + static_cast<int64_t>(first_up + grp) * kCounterStride;
+    if (!arrive_last(ctr, gsize, flag)) return false;  // the last arriver stores 0 there again
     const double *children = L.slabs[l] + static_cast<int64_t>(first_l + grp * kFanIn) * E;
     if (is_root) {
       *root = L.slabs[l] + static_cast<int64_t>(first_l) * E;
@@ -914,6 +943,25 @@ __device__ __forceinline__ int gather_entry(int p, int rows) {
   return r >= 0 ? Sch::GRAM + 2 * r : -1;
 }
 
+// The same slots without the used-pairs test: every Gram pair, the never-used hosts still
+// carrying their row-sum pair.  Up to T = 10 (GRAM <= 256) the test in front of the loads costs
+// more than the loads it saves, as in the one-group path: C2 cycle, 20-slab root, 10.01 -> 9.92
+// and 9.60 -> 9.48 us with the counters spread (build knob, profiles/r09).
+#ifndef CCMPC_SPREAD_ALL_PAIRS
+#define CCMPC_SPREAD_ALL_PAIRS 1
+#endif
+// Build knob: a two-group root (17 .. 32 slabs, GRAM <= 256) with its groups in the two halves
+// of every wave (gather_root).  The 20-slab gather 1.40 -> 1.01 us, as long as a one-group one
+// (1.08); C2 cycle 9.48 -> 9.32 us (profiles/r09).
+#ifndef CCMPC_PAIR_WAVE_GATHER
+#define CCMPC_PAIR_WAVE_GATHER 1
+#endif
+template <typename Sch>
+__device__ __forceinline__ int gather_entry_all(int p) {
+  const int r = Sch::hosted_row_pair(2 * p);
+  return r >= 0 ? Sch::GRAM + 2 * r : 2 * p;
+}
+
 // LDS doubles gather_root needs beside its destination: one slab per further group of a root.
 __host__ __device__ constexpr int gather_part_doubles(int E) {
   return (CCMPC_ROOT_FANIN / kFanIn - 1) * E;
@@ -935,18 +983,24 @@ __host__ __device__ constexpr int gather_part_doubles(int E) {
 //    that needs one.  Group 0 lands in dst_lds, group q > 0 in part_lds + (q - 1) E
 //    (gather_part_doubles(E) doubles); after a barrier the groups are added in index order,
 //    ((G0 + G1) + G2) + G3, each group sum being sum_group2's left-to-right chain: the bits of a
-//    group-by-group gather.  Only the pairs finalize_cell uses are loaded and written here --
-//    the Gram pairs with a position on or above the diagonal inside the 2T live rows
-//    (pair_use), and every row-sum pair -- which is what lets two groups' slots fit one
-//    workgroup; the rest of dst_lds is left as it was and must not be read.  Passes: ceil(groups HP / threads) -- with 256 threads, at T <= 10
-//    (HP = 128) one for <= 32 slabs and two for <= 64; wider Grams take more slots than threads
-//    and proportionally more passes, never more than the per-thread group loop took.
+//    group-by-group gather.  Above T = 10 only the pairs finalize_cell uses are loaded and
+//    written here -- the Gram pairs with a position on or above the diagonal inside the 2T live
+//    rows (pair_use), and every row-sum pair; up to T = 10 every slot loads (gather_entry_all).
+//    Either way the row-sum pairs ride in never-used slots, which is what lets two groups' slots
+//    fit one workgroup, and those slots' own entries of dst_lds are left as they were and must
+//    not be read.  Passes: ceil(groups HP / threads) -- with 256 threads, at T <= 10 (HP = 128)
+//    two for 33 .. 64 slabs; wider Grams take more slots than threads and proportionally more
+//    passes, never more than the per-thread group loop took.
+//  * kFanIn < n <= 2 kFanIn up to T = 10: the same slots, but the two groups of a slot sit in
+//    lanes l and l + 32 of one wave and meet by a cross-lane move, G0 + G1 in the lower lane:
+//    no LDS meeting point, one barrier less, the same bits.
 // The branch on root_n is workgroup-uniform.  Ends with a barrier.
 template <typename Sch>
 __device__ __forceinline__ void gather_root(const double *__restrict__ root, int32_t root_n,
                                             int rows, double *dst_lds, double *part_lds) {
   constexpr int E = Sch::E, GRAM = Sch::GRAM, H = Sch::GRAM / 2;
   constexpr int HP = (H + 63) / 64 * 64;  // a group's slots, padded to whole waves
+  constexpr bool kAllPairs = CCMPC_SPREAD_ALL_PAIRS && GRAM <= 256;  // T <= 10
   const int tid = threadIdx.x, nth = blockDim.x;
   if (root_n <= kFanIn || root_n > kRootFanIn || !part_lds) {
     // (a root wider than kRootFanIn exists only at the tree's depth bound; it, and a caller
@@ -965,13 +1019,44 @@ __device__ __forceinline__ void gather_root(const double *__restrict__ root, int
     __syncthreads();
     return;
   }
+  if (CCMPC_PAIR_WAVE_GATHER && GRAM <= 256 && root_n <= 2 * kFanIn) {
+    // 17 .. 32 slabs up to T = 10: the two groups of a slot meet in ONE wave -- lane l < 32 sums
+    // group 0's pair, lane l + 32 group 1's, and a cross-lane move brings G1 to G0's lane, so
+    // there is no LDS meeting point, no barrier and no second pass.  One descriptor over the
+    // whole root: group 0 is full, and group 1's loads past slab root_n - 1 are past its end.
+    // Every slot loads (gather_entry_all), each group sum is sum_group2's chain, then G0 + G1.
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double *>(root), 0, static_cast<int>(root_n) * E * 8, 0x00020000);
+    for (int s = tid; s < 2 * HP; s += nth) {  // whole waves: every lane takes part in the move
+      const int p = ((s >> 6) << 5) + (s & 31), q = (s >> 5) & 1;
+      const int e = p < H ? gather_entry_all<Sch>(p) : -1;  // the same in lanes l and l + 32
+      const int n_q = q ? root_n - kFanIn : kFanIn;
+      const int at = 8 * (q * kFanIn * E + (e < 0 ? 0 : e));
+      double2 v[kFanIn];
+#pragma unroll
+      for (int i = 0; i < kFanIn; ++i) v[i] = ld2_sc1(rs, at + 8 * (i * E));
+      double2 g = v[0];
+#pragma unroll
+      for (int i = 1; i < kFanIn; ++i) {
+        g.x += (i < n_q) ? v[i].x : 0.0;
+        g.y += (i < n_q) ? v[i].y : 0.0;
+      }
+      const double ox = __shfl_xor(g.x, 32, 64), oy = __shfl_xor(g.y, 32, 64);
+      if (q == 0 && e >= 0) {
+        dst_lds[e] = g.x + ox;
+        dst_lds[e + 1] = g.y + oy;
+      }
+    }
+    __syncthreads();
+    return;
+  }
   const int ng = (root_n + kFanIn - 1) >> kLgFanIn;
   for (int s = tid; s < ng * HP; s += nth) {
     // a wave's 64 slots are in one group (HP and the workgroup are whole waves), so the group's
     // base and slab count stay in scalar registers, as in the one-group path
     const int q = __builtin_amdgcn_readfirstlane(s / HP);
     const int p = s - q * HP;
-    const int e = p < H ? gather_entry<Sch>(p, rows) : -1;
+    const int e = p < H ? (kAllPairs ? gather_entry_all<Sch>(p) : gather_entry<Sch>(p, rows)) : -1;
     if (e < 0) continue;
     const double2 g = sum_group2(root + static_cast<int64_t>(q * kFanIn) * E,
                                  min(root_n - q * kFanIn, kFanIn), E, e);
@@ -981,10 +1066,11 @@ __device__ __forceinline__ void gather_root(const double *__restrict__ root, int
   }
   __syncthreads();
   for (int e = 2 * tid; e < E; e += 2 * nth) {
-    if (e < GRAM) {
+    if (!kAllPairs && e < GRAM) {
       const PairUse u = pair_use<Sch>(e, rows);
       if (!u.use0 && !u.use1) continue;
     }
+    // (kAllPairs: a host pair's own slot was never written; its sum is never read either)
     double2 s = {dst_lds[e], dst_lds[e + 1]};
     for (int q = 1; q < ng; ++q) {  // fixed order: deterministic
       s.x += part_lds[(q - 1) * E + e];

@@ -24,11 +24,7 @@
 //    slabs write-through and meet in the fixed fan-in-16 tree.  The cell's finaliser then
 //    (cycle variant) builds its T(T-1)/2 half-spaces from the covariance it just produced in
 //    LDS -- no kernel boundary between moments and constraints.
-#include "constraints.hpp"
-#include <algorithm>
-#include <type_traits>
-
-#include "gram.hpp"
+#include "ccmpc_common.hpp"
 
 #ifndef CCMPC_PROBE
 #define CCMPC_PROBE 0
@@ -65,6 +61,22 @@ __device__ unsigned long long g_probe_ts[kProbeMaxWG * kProbeSlots];
   do {                   \
   } while (0)
 #endif
+
+// ... and slot 2 = the arrival's drain and barrier done, just before the ticket's add is issued
+// (gram.hpp arrive_last; it overwrites the stream's end, which the cell timeline does not use)
+#if (CCMPC_PROBE & 4) && (CCMPC_PROBE & 16)
+#define PROBE_DRAINED()                                                                        \
+  do {                                                                                         \
+    if (threadIdx.x == 0 && blockIdx.x < kProbeMaxWG)                                          \
+      g_probe_ts[blockIdx.x * kProbeSlots + 2] = __builtin_amdgcn_s_memrealtime();             \
+  } while (0)
+#endif
+
+#include "constraints.hpp"
+#include <algorithm>
+#include <type_traits>
+
+#include "gram.hpp"
 
 namespace ccmpc {
 

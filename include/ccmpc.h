@@ -153,8 +153,8 @@ int ccmpc_graph_destroy(void *exec);
  * the result is deterministic and uses no float atomics.
  *
  * Workspace contract (every *_workspace_bytes-sized workspace): its first
- * round_up(workspace_bytes / 32, 256) bytes hold the tree's arrival counters, the rest the
- * partial-Gram slabs.  Zero-fill a fresh workspace ONCE (hipMemset after allocating); every
+ * round_up(workspace_bytes / 8, 256) bytes hold the tree's arrival counters (one per 128-byte
+ * line), the rest the partial-Gram slabs.  Zero-fill a fresh workspace ONCE (hipMemset after allocating); every
  * call leaves the counters zero again.  One workspace may serve calls of ANY shape (moments,
  * cycles, ideal rollouts, any T / cell count) as long as every call passes the same
  * workspace_bytes (the whole buffer) and that is >= the call's *_workspace_bytes: the counter
