@@ -142,7 +142,7 @@ SIGNATURES = {
     "ccmpc_poison_lds": (ctypes.c_int, [_D, _P]),
 }
 
-SELFTEST_MVOE, SELFTEST_TANGENT, SELFTEST_BOUND, SELFTEST_PAIR = 0, 1, 2, 3
+SELFTEST_MVOE, SELFTEST_TANGENT, SELFTEST_BOUND, SELFTEST_PAIR, SELFTEST_PRIM = 0, 1, 2, 3, 4
 
 
 class CycleArgs(ctypes.Structure):

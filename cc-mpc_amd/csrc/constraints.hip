@@ -58,6 +58,10 @@ __global__ __launch_bounds__(64) void affine_kernel(
   h.t = t;
   const M2 c = block(C, rows, t, t);
   // sqrtm of a 2x2 SPD matrix: (A + sqrt(det) I) / sqrt(tr + 2 sqrt(det))   (:1494)
+  // The plain difference keeps the sign of the exact a d - b c whenever that is >= 0 (rounding
+  // is monotone: a d >= b c gives fl(a d) >= fl(b c)), so a PSD matrix is never flagged; on a
+  // nearly collinear cloud det loses its digits, which margin and rhs feel less than the
+  // reference's own sqrtm does (tests/test_gpu_tail_precision.py, near-singular covariances).
   const double det = c.a * c.d - c.b * c.c;
   double s00 = NAN, s01 = NAN, s11 = NAN;
   if (det >= 0.0 && c.a + c.d > 0.0) {

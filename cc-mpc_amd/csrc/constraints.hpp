@@ -31,9 +31,10 @@ __device__ __forceinline__ M2 transpose(const M2 &x) { return {x.a, x.c, x.b, x.
 
 // Latency-lean f64 reciprocal and square root for the MVOE chain (a serial dependency chain per
 // record, so each IEEE div / sqrt fix-up sequence is pure latency): hardware estimate + Newton /
-// Goldschmidt refinement, <= ~2 ulp on the well-scaled values here (covariances, beta ~ 1),
-// against the 1e-5 relative Frobenius parity bar on Q.  The tangent choice and side test keep
-// IEEE division, so which / side stay decided exactly as the reference decides them.
+// Goldschmidt refinement, <= 2 ulp (tests/test_gpu_tail_precision.py asserts it over
+// [2^-200, 2^200] and measures 0.5), against the 1e-5 relative Frobenius parity bar on Q.
+// The tangent choice and side test keep IEEE division, so which / side stay decided exactly
+// as the reference decides them.
 __device__ __forceinline__ double rcp_nr(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = fma(fma(-x, r, 1.0), r, r);
@@ -83,6 +84,22 @@ __device__ __forceinline__ bool solve2(const M2 &s1, const M2 &s2, M2 &out) {
   return true;
 }
 
+// One update of the MVOE fixed point, beta' = N rsqrt(N D) with N = 2 + s beta and
+// D = s + p2 beta (p2 = 2 l1 l2); see compute_mvoe.  Shared with CCMPC_SELFTEST_PRIM.
+__device__ __forceinline__ double mvoe_step(double s, double p2, double b) {
+  const double N = fma(s, b, 2.0), D = fma(p2, b, s);
+  const double x = N * D;
+  const double y = __builtin_amdgcn_rsq(x);
+  // y = rsqrt(x) (1 + e) gives r = 1 - x y^2 = -(2 e + e^2), and (1 + e) (1 + r / 2 + 3/8 r^2) =
+  // 1 + O(e^3): the second-order step on A = N y.  The first-order one, (1 + r / 2), is 3/2 e^2
+  // off -- 17 ulp with the hardware estimate's e ~ 2^-24 -- at the same number of operations
+  // and the same depth of chain (a product and an fma after r; A does not wait for r).
+  const double g = x * y;
+  const double r = fma(-g, y, 1.0);
+  const double A = N * y;
+  return fma(A * r, fma(0.375, r, 0.5), A);
+}
+
 // makeconstraint.py:7-38
 __device__ bool compute_mvoe(const M2 &S1, const M2 &S2, double tol, int maxiter, double &beta,
                              M2 &Q) {
@@ -96,19 +113,15 @@ __device__ bool compute_mvoe(const M2 &S1, const M2 &S2, double tol, int maxiter
   const double l1 = half_tr + sd, l2 = half_tr - sd;
   // beta' = sqrt(sum 1/w / sum l/w), w = 1 + beta l  ==  sqrt(N / D) with N = w1 + w2 =
   // 2 + s beta and D = l1 w2 + l2 w1 = s + 2 p beta (s = l1 + l2, p = l1 l2)  ==  N rsqrt(N D):
-  // the same fixed point, each step one product, one hardware rsqrt and one Goldschmidt step
-  // (7 dependent f64 operations, against 17 for an IEEE division + square root; the iteration
-  // is a serial chain per record, so its latency is the tail's critical path).  Rounding
-  // differs from the reference's order by a few ulp per step; the contraction damps it.
+  // the same fixed point, each step one product, one hardware rsqrt and one second-order
+  // Goldschmidt step (7 dependent f64 operations, against 17 for an IEEE division + square
+  // root; the iteration is a serial chain per record, so its latency is the tail's critical
+  // path).  One step is within a few ulp of the exact sqrt(N / D): <= 2 ulp of rounding plus
+  // O(e^3) (tests/test_gpu_tail_precision.py asserts <= 8 and gives the measured figure).
   const double s = l1 + l2, p2 = 2.0 * (l1 * l2);
   double b = 1.0;
   for (int it = 0; it < maxiter; ++it) {
-    const double N = fma(s, b, 2.0), D = fma(p2, b, s);
-    const double x = N * D;
-    const double y = __builtin_amdgcn_rsq(x);
-    const double g = x * y, h = 0.5 * y;
-    const double r = fma(-g, h, 0.5);
-    const double bn = (2.0 * N) * fma(h, r, h);
+    const double bn = mvoe_step(s, p2, b);
     const bool done = fabs(bn - b) < tol;
     b = bn;
     if (done) break;

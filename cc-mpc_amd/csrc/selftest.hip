@@ -70,6 +70,15 @@ __global__ __launch_bounds__(64) void selftest_kernel(int kind, int64_t n,
       y[13] = pair_scale(pm, x[17], x[16]);
       break;
     }
+    case CCMPC_SELFTEST_PRIM: {  // the hand-made primitives under the MVOE chain
+      const double a = in[i * 2], b = in[i * 2 + 1];
+      double *y = out + i * 4;
+      y[0] = rcp_nr(b);
+      y[1] = div_nr(a, b);
+      y[2] = sqrt_gs(b);
+      y[3] = mvoe_step(b, 1.0, a);  // one fixed-point update from beta = a with s = b, p2 = 1
+      break;
+    }
     default:
       break;
   }
@@ -106,7 +115,7 @@ extern "C" int ccmpc_poison_lds(double value, ccmpc_stream_t stream) {
 
 extern "C" int ccmpc_selftest(int kind, int64_t n, const double *in, double *out, double tol,
                               int32_t maxiter, ccmpc_stream_t stream) {
-  CCMPC_REQUIRE(kind >= CCMPC_SELFTEST_MVOE && kind <= CCMPC_SELFTEST_PAIR, "unknown kind");
+  CCMPC_REQUIRE(kind >= CCMPC_SELFTEST_MVOE && kind <= CCMPC_SELFTEST_PRIM, "unknown kind");
   CCMPC_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "bad n");
   if (n == 0) return CCMPC_OK;
   CCMPC_REQUIRE(in && out, "null pointer");

@@ -709,11 +709,15 @@ int ccmpc_risk_audit(const void *positions, int dtype, int64_t ld, int64_t T,
  *  PAIR     in[n][18] = 4x4 cov of (x_tau, y_tau, x_t, y_t), Gamma, chi_p
  *           out[n][14] = cov_infer, cov_mu, cov_t, lower bound, scale
  *           (predict_moments, makeconstraint.py:41-70, then BOUND)
+ *  PRIM     in[n][2]  = a, b      out[n][4] = rcp_nr(b), div_nr(a, b), sqrt_gs(b), and one
+ *           update of the MVOE fixed point from beta = a with s = b, p2 = 1
+ *           (the hand-made reciprocal / division / square root of the MVOE chain)
  * ------------------------------------------------------------------------------------- */
 #define CCMPC_SELFTEST_MVOE 0
 #define CCMPC_SELFTEST_TANGENT 1
 #define CCMPC_SELFTEST_BOUND 2
 #define CCMPC_SELFTEST_PAIR 3
+#define CCMPC_SELFTEST_PRIM 4
 int ccmpc_selftest(int kind, int64_t n, const double *in, double *out, double tol,
                    int32_t maxiter, ccmpc_stream_t stream);
 
