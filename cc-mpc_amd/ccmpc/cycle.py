@@ -155,6 +155,13 @@ class MinkowskiCycle:
                                  rec_kind=engine._lib.REC_KIND_HALFSPACE, R=self.R,
                                  cell_plan=cell_plan, out=out)
 
+    def calibrate(self, allow=None, out=None):
+        """Monte-Carlo calibration (engine.risk_quantile) of this cycle's half-spaces on its own
+        particle store, at its R: the offsets that leave at most allow[c] particles of a cell
+        open.  Call after run() / replay(); engine.calibrated_records applies the result."""
+        return engine.risk_quantile(self.store, self.rec, engine._lib.REC_KIND_HALFSPACE,
+                                    allow=allow, R=self.R, out=out)
+
 
 class AffineCycle:
     def __init__(self, store, K, ref_traj, ph=None, R=risk.R_COLLISION, scene_K=None,
@@ -197,3 +204,9 @@ class AffineCycle:
         return engine.risk_audit(self.store, plan=plan, rec=self.rec,
                                  rec_kind=engine._lib.REC_KIND_AFFINE, R=self.R,
                                  cell_plan=cell_plan, out=out)
+
+    def calibrate(self, allow=None, out=None):
+        """Monte-Carlo calibration (engine.risk_quantile) of this cycle's affine half-spaces on
+        its own particle store, at its R.  Call after run()."""
+        return engine.risk_quantile(self.store, self.rec, engine._lib.REC_KIND_AFFINE,
+                                    allow=allow, R=self.R, out=out)

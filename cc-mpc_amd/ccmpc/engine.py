@@ -746,6 +746,154 @@ def risk_audit(store, plan=None, rec=None, rec_kind=None, R=risk.R_COLLISION, ce
     return out
 
 
+RiskQuantile = collections.namedtuple("RiskQuantile", "q rhs status workspace")
+RiskQuantile.__doc__ = """risk_quantile's device tensors: q [C, P] float64 (the (m+1)-th largest
+projection), rhs [C, P] float64 (the offset that protects it), status [C, P] int32 (0, or
+_lib.CAL_VACUOUS / CAL_SKIPPED), and the workspace buffer the call owns.  See
+ccmpc_risk_quantile in include/ccmpc.h."""
+
+_REC_KINDS = (_lib.REC_KIND_HALFSPACE, _lib.REC_KIND_AFFINE, _lib.REC_KIND_HALFSPACE_COMPACT,
+              _lib.REC_KIND_AFFINE_COMPACT)
+
+
+def _rec_layout(rec_kind):
+    """(record bytes, byte offset of the rhs field, byte offset and width of side)."""
+    if rec_kind == _lib.REC_KIND_HALFSPACE:
+        f = _lib.HALFSPACE_DTYPE.fields
+        return 128, f["d"][1], f["side"][1], 4
+    if rec_kind == _lib.REC_KIND_AFFINE:
+        f = _lib.AFFINE_DTYPE.fields
+        return 128, f["rhs"][1], f["side"][1], 4
+    f = _lib.GATHER_DTYPE.fields
+    return _lib.GATHER_DTYPE.itemsize, f["rhs"][1], f["side"][1], 2
+
+
+def _rec_bytes(rec, rec_kind, C):
+    if rec_kind not in _REC_KINDS:
+        raise ValueError(f"unknown rec_kind {rec_kind!r}")
+    width = _rec_layout(rec_kind)[0]
+    if rec.dtype != torch.uint8:
+        rec = rec.view(torch.uint8)
+    rec = rec.reshape(C, -1, width) if rec.dim() != 3 else rec
+    if rec.shape[0] != C or rec.shape[2] != width:
+        raise ValueError(f"rec must be ({C}, P, {width}) bytes for rec_kind {rec_kind}")
+    return rec
+
+
+def record_fields(rec, rec_kind):
+    """Host (n0, n1, rhs, side, status, t) arrays [C, P] of device (or host) record bytes of
+    any of the four kinds: the fields ccmpc_risk_audit / ccmpc_risk_quantile read."""
+    b = rec.detach().cpu().numpy() if torch.is_tensor(rec) else np.asarray(rec)
+    b = np.ascontiguousarray(b).view(np.uint8)
+    half = rec_kind in (_lib.REC_KIND_HALFSPACE, _lib.REC_KIND_HALFSPACE_COMPACT)
+    if rec_kind == _lib.REC_KIND_HALFSPACE:
+        h = b.view(_lib.HALFSPACE_DTYPE)[..., 0]
+        rhs, t = h["d"], h["t_tau"]
+    elif rec_kind == _lib.REC_KIND_AFFINE:
+        h = b.view(_lib.AFFINE_DTYPE)[..., 0]
+        rhs, t = h["rhs"], h["t"]
+    else:
+        h = b.view(_lib.GATHER_DTYPE)[..., 0]
+        rhs, t = h["rhs"], h["t_tau"]
+    t = t.astype(np.int64) >> 16 if half else t.astype(np.int64)
+    return (h["n0"].copy(), h["n1"].copy(), rhs.copy(), h["side"].astype(np.float64),
+            h["status"].astype(np.int64), t)
+
+
+def risk_quantile(store, rec, rec_kind, allow=None, R=risk.R_COLLISION, T=None, out=None):
+    """Monte-Carlo calibration of record offsets on a ParticleStore (ccmpc_risk_quantile): per
+    record, the (allow[c] + 1)-th largest projection side * (n . p) of the cell's particles at
+    the record's step, and the smallest offset for which the audit's predicate protects it --
+    the offset that leaves at most allow[c] particles of the cell open.
+
+    rec / rec_kind / R / T as risk_audit.  allow: particles a record may leave open, per cell:
+    None (zeros), a host sequence (checked to be >= 0 here) or an int64 device tensor [C] (read
+    unchecked; a negative entry marks the cell's records SKIPPED), e.g. risk.allow_counts.
+    out: a previous RiskQuantile whose buffers and workspace are used again (nothing is allocated
+    then, so the call can be captured).  Returns RiskQuantile; enqueues 17 launches on the
+    current stream, never synchronises."""
+    lib = _lib.load()
+    dev = store.device
+    C = store.n_cells
+    T = store.T if T is None else int(T)
+    if not 1 <= T <= store.T:
+        raise ValueError(f"T = {T} outside [1, {store.T}] (the store's horizon)")
+    if getattr(store, "offsets", None) and any(int(o) % 4 for o in store.offsets):
+        raise ValueError("cell offsets must be multiples of 4 particles")
+    if rec is None:
+        raise ValueError("risk_quantile needs records")
+    rec = _rec_bytes(rec, rec_kind, C)
+    P = _audit_rows(rec_kind, T)
+    if rec.shape[1] < P:
+        raise ValueError(f"rec holds {rec.shape[1]} rows per cell, T = {T} needs {P}")
+    if P and (rec.shape[1] != P or not rec.is_contiguous()):
+        rec = rec[:, :P].contiguous()       # rows of a longer horizon's buffer
+    if allow is None:
+        pass
+    elif torch.is_tensor(allow):
+        if (allow.dtype != torch.int64 or tuple(allow.shape) != (C,) or allow.device != dev
+                or not allow.is_contiguous()):
+            raise ValueError(f"allow must be a contiguous int64 [{C}] tensor on {dev}")
+    else:
+        host = np.asarray(allow, np.int64).reshape(-1)
+        if host.shape[0] != C or (C and host.min() < 0):
+            raise ValueError(f"allow must hold {C} counts >= 0")
+        allow = torch.as_tensor(host, device=dev)
+    need = int(lib.ccmpc_risk_quantile_workspace_bytes(T, int(rec_kind), C))
+    if need == 0:
+        raise ValueError(f"ccmpc_risk_quantile rejects T = {T}, rec_kind = {rec_kind}")
+    if out is None:
+        out = RiskQuantile(torch.empty((C, P), dtype=torch.float64, device=dev),
+                           torch.empty((C, P), dtype=torch.float64, device=dev),
+                           torch.empty((C, P), dtype=torch.int32, device=dev),
+                           torch.empty(need, dtype=torch.uint8, device=dev))
+    else:
+        for name in ("q", "rhs", "status"):
+            t = getattr(out, name)
+            if t is None or tuple(t.shape) != (C, P) or not t.is_contiguous():
+                raise ValueError(f"out.{name} must be a contiguous {(C, P)} tensor")
+        if out.workspace is None or out.workspace.numel() < need:
+            raise ValueError(f"out.workspace must hold {need} bytes")
+    if C == 0:
+        return out
+    _lib.check(lib.ccmpc_risk_quantile(
+        _p(store.pos), store.ccmpc_dtype, store.ld, T, _p(store.origin), _p(store.cell_off),
+        _p(store.cell_cnt), C, store.n_bound, _p(rec), int(rec_kind), float(R), _p(allow),
+        _p(out.workspace), out.workspace.numel(), _p(out.q), _p(out.rhs), _p(out.status),
+        _stream()), "ccmpc_risk_quantile")
+    return out
+
+
+def calibrated_records(rec, rec_kind, quant, mode="replace"):
+    """A new uint8 tensor of `rec`'s layout whose rhs field (d of the half-space record, rhs of
+    the affine record and of the compact packing) carries risk_quantile's offsets; `rec` itself
+    is never written.  Device tensor ops only, no host round trip.
+      "replace"  rhs <- quant.rhs
+      "tighten"  whichever has the larger side*rhs: never less constrained than the analytic one
+      "relax"    whichever has the smaller side*rhs
+    Records that are VACUOUS or SKIPPED keep their rhs in every mode, as do rows past quant's."""
+    if mode not in ("replace", "tighten", "relax"):
+        raise ValueError(f"mode must be 'replace', 'tighten' or 'relax', not {mode!r}")
+    C = int(quant.rhs.shape[0])
+    out = _rec_bytes(rec, rec_kind, C).clone(memory_format=torch.contiguous_format)
+    P = int(quant.rhs.shape[1])
+    if out.shape[1] < P:
+        raise ValueError(f"rec holds {out.shape[1]} rows per cell, the calibration {P}")
+    if P == 0:
+        return out
+    _, o_rhs, o_side, w_side = _rec_layout(rec_kind)
+    field = out[:, :P, o_rhs:o_rhs + 8].view(torch.float64)[..., 0]
+    side = out[:, :P, o_side:o_side + w_side].view(
+        torch.int32 if w_side == 4 else torch.int16)[..., 0].to(torch.float64)
+    sel = quant.status == 0
+    if mode == "tighten":
+        sel = sel & (side * quant.rhs > side * field)
+    elif mode == "relax":
+        sel = sel & (side * quant.rhs < side * field)
+    field.copy_(torch.where(sel, quant.rhs, field))
+    return out
+
+
 def bucket(z, sample_store, latent_pmf, minpos, filter_pmf=0.1, max_k=None):
     """GPU bucketing (ccmpc_bucket) of a sampler output (z [O,N], sample-order F32 store with
     one cell per OV) into kept-mode cells.  latent_pmf (O, L) is host data, as in the reference

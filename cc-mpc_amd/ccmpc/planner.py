@@ -1409,6 +1409,41 @@ class MidlevelAgent:
                               R=self.R if R is None else float(R), T=T)
         return risk.audit_report(a, scene.store.counts, K, self.prediction_horizon)
 
+    def calibrate_constraints(self, R=None, eps=None, mode=None):
+        """Monte-Carlo calibration of the last predict_and_constrain /
+        predict_and_constrain_affine frame's records on its sampled scene
+        (engine.risk_quantile on the step graph's bucketed store): the offsets that leave at most
+        risk.allow_counts(...) particles of each cell open at the record's step, for the per-step
+        budget eps / O / ph (eps default: risk.EPS_TOTAL; R default: the agent's).  Needs the
+        frame's records to have been generated from that store, i.e. Tsh == ph (below ph they
+        come from the ideal rollout, which is never materialised: raises RuntimeError).  The
+        store must be read before the next step of the same shape (raises after it), as for
+        audit_plan.  Never called implicitly and changes no planner state.
+        Returns risk.calibration_report's dict; with mode ("replace", "tighten" or "relax") a
+        pair (report, records): engine.calibrated_records' device tensor in the layout
+        ccmpc_mpc_qp reads, the frame's own records left as they are."""
+        if self._audit_src is None:
+            raise RuntimeError("no sampled scene: call predict_and_constrain or "
+                               "predict_and_constrain_affine first")
+        scene, K, T, last = self._audit_src
+        scene.check_live()
+        if last is None:
+            raise RuntimeError(f"the last frame (Tsh = {T} < ph) has no materialised records: "
+                               "its half-spaces come from the ideal rollout")
+        kind = last[1]
+        rec = engine._rec_bytes(last[0], kind, scene.store.n_cells)
+        eps = risk.EPS_TOTAL if eps is None else float(eps)
+        ph = self.prediction_horizon
+        counts = scene.store.counts
+        allow = risk.allow_counts(counts, K, ph, eps)
+        quant = engine.risk_quantile(scene.store, rec, kind, allow=allow,
+                                     R=self.R if R is None else float(R), T=T)
+        report = risk.calibration_report(quant, engine.record_fields(rec, kind),
+                                         counts, K, ph, eps)
+        if mode is None:
+            return report
+        return report, engine.calibrated_records(rec, kind, quant, mode)
+
     def _qp_launch(self, x_init, goal, ref_traj, T, rec, kind, u_prev, lon, u_order):
         """Enqueue solve_planning_qp's device work on the current stream (no wait): the LTV
         rebuild at Tsh == ph, the QP on `rec`, the answer's copy-out and signal."""

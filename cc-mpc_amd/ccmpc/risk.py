@@ -65,6 +65,15 @@ def _np(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
+def _cell_budgets(K, ph, eps):
+    """(budget_traj [C], budget_step [C]) = eps_ura[o, k] and eps_ura[o, k] / ph, cells in
+    (ov, k) order."""
+    K = [int(k) for k in K]
+    e = eps_ura(K, eps)
+    traj = np.array([e[o, k] for o, k_o in enumerate(K) for k in range(k_o)], np.float64)
+    return traj, traj / ph
+
+
 def audit_report(audit, counts, K, ph, eps=EPS_TOTAL):
     """Host-side report of an engine.RiskAudit (device tensors or arrays) against the risk
     budget: counts [n_cells] particles per cell, K modes per OV (cells in (ov, k) order), ph the
@@ -84,9 +93,7 @@ def audit_report(audit, counts, K, ph, eps=EPS_TOTAL):
     n = np.asarray(counts, np.float64).reshape(-1)
     if n.shape[0] != sum(K):
         raise ValueError(f"{n.shape[0]} cell counts for {sum(K)} cells")
-    e = eps_ura(K, eps)
-    budget_traj = np.array([e[o, k] for o, k_o in enumerate(K) for k in range(k_o)], np.float64)
-    budget_step = budget_traj / ph
+    budget_traj, budget_step = _cell_budgets(K, ph, eps)
     hit, hit_any, min_d2 = _np(audit.hit), _np(audit.hit_any), _np(audit.min_d2)
     rec_open, opn = _np(audit.rec_open), _np(audit.open)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -108,3 +115,50 @@ def audit_report(audit, counts, K, ph, eps=EPS_TOTAL):
             out["worst"] = (int(c), int(t))
             out["worst_p_hit"] = float(p_hit[c, t])
     return out
+
+
+def allow_counts(counts, K, ph, eps=EPS_TOTAL):
+    """(n_cells,) int64 = floor(eps_ura[o, k] / ph * N_c): the particles of cell c a record may
+    leave open without exceeding the per-step budget audit_report sets its counts beside
+    (engine.risk_quantile's `allow`).  0 for an empty cell."""
+    n = np.asarray(counts, np.float64).reshape(-1)
+    if n.shape[0] != sum(int(k) for k in K):
+        raise ValueError(f"{n.shape[0]} cell counts for {sum(int(k) for k in K)} cells")
+    return np.floor(_cell_budgets(K, ph, eps)[1] * n).astype(np.int64)
+
+
+def calibration_report(quant, fields, counts, K, ph, eps=EPS_TOTAL):
+    """Host-side report of an engine.RiskQuantile (device tensors or arrays) beside the analytic
+    records it calibrated.  fields: the records' (n0, n1, rhs, side, ...) arrays [C, P]
+    (engine.record_fields); counts [n_cells], K and ph as audit_report.  Reports only.  Returns
+    a dict of NumPy arrays --
+      status [C, P]        0 calibrated, 1 vacuous (allow >= N_c), 2 skipped
+      q, rhs_cal [C, P]    the selected projection and the calibrated offset; rhs the analytic one
+      slack [C, P]         side*rhs - side*rhs_cal: how far the analytic record stands beyond the
+                           empirical one (positive) or short of it (negative); nan where the
+                           record is not calibrated
+      slack_m [C, P]       slack / |n|, in metres
+      counts [C], budget_step [C] = eps_ura[o, k] / ph, allow [C] = allow_counts(...)
+      worst_rec [C]        the calibrated record with the smallest slack_m (-1: none),
+      worst_slack_m [C]    its slack_m (nan: none)."""
+    n = np.asarray(counts, np.float64).reshape(-1)
+    status = _np(quant.status).astype(np.int64)
+    q, rhs_cal = _np(quant.q), _np(quant.rhs)
+    C, P = status.shape
+    if n.shape[0] != C:
+        raise ValueError(f"{n.shape[0]} cell counts for {C} cells")
+    n0, n1, rhs, side = (np.asarray(f, np.float64)[:, :P] for f in tuple(fields)[:4])
+    cal = status == 0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        slack = np.where(cal, side * rhs - side * rhs_cal, np.nan)
+        slack_m = slack / np.sqrt(n0 * n0 + n1 * n1)
+    worst_rec = np.full(C, -1, np.int64)
+    worst = np.full(C, np.nan)
+    for c in range(C):
+        ok = cal[c] & ~np.isnan(slack_m[c])
+        if ok.any():
+            p = int(np.argmin(np.where(ok, slack_m[c], np.inf)))
+            worst_rec[c], worst[c] = p, slack_m[c, p]
+    return dict(status=status, q=q, rhs_cal=rhs_cal, rhs=rhs, slack=slack, slack_m=slack_m,
+                counts=n.astype(np.int64), budget_step=_cell_budgets(K, ph, eps)[1],
+                allow=allow_counts(n, K, ph, eps), worst_rec=worst_rec, worst_slack_m=worst)

@@ -28,70 +28,10 @@
 
 #include <type_traits>
 
-#include "gram.hpp"
-
 namespace ccmpc {
 
 constexpr int kAuditThreads = 256;
 constexpr int kAuditU = 4;  // steps per load group
-
-template <typename P>
-struct AuditVec;
-template <>
-struct AuditVec<double> {
-  static constexpr int W = 2;
-  double2 v;
-  __device__ __forceinline__ void load(const double *p) { v = stream_load2<true>(p); }
-  __device__ __forceinline__ double operator[](int j) const { return j ? v.y : v.x; }
-};
-template <>
-struct AuditVec<float> {
-  static constexpr int W = 4;
-  float4 v;
-  __device__ __forceinline__ void load(const float *p) {
-    const ccmpc_f4v t = __builtin_nontemporal_load(reinterpret_cast<const ccmpc_f4v *>(p));
-    v = make_float4(t.x, t.y, t.z, t.w);
-  }
-  __device__ __forceinline__ double operator[](int j) const {
-    return static_cast<double>(j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w);
-  }
-};
-
-// The fields of a record the audit reads, from any of the four kinds.
-struct AuditRec {
-  double n0, n1, rhs;
-  int side, status, t;
-};
-__device__ __forceinline__ AuditRec audit_read_rec(const unsigned char *__restrict__ rec,
-                                                   int kind, int64_t i) {
-  AuditRec q;
-  if (kind == CCMPC_REC_KIND_HALFSPACE || kind == CCMPC_REC_KIND_AFFINE) {
-    const unsigned char *r = rec + i * 128;
-    const double2 nn = *reinterpret_cast<const double2 *>(r);
-    const int4 tail = *reinterpret_cast<const int4 *>(r + 112);  // which, side, status, t(_tau)
-    q.n0 = nn.x;
-    q.n1 = nn.y;
-    q.rhs = *reinterpret_cast<const double *>(r + (kind == CCMPC_REC_KIND_AFFINE ? 32 : 16));
-    q.side = tail.y;
-    q.status = tail.z;
-    q.t = kind == CCMPC_REC_KIND_AFFINE ? tail.w : (tail.w >> 16);
-  } else {  // ccmpc_gather_rec
-    const unsigned char *r = rec + i * 32;
-    const double2 nn = *reinterpret_cast<const double2 *>(r);
-    const uint2 w = *reinterpret_cast<const uint2 *>(r + 24);
-    q.n0 = nn.x;
-    q.n1 = nn.y;
-    q.rhs = *reinterpret_cast<const double *>(r + 16);
-    q.side = static_cast<int16_t>(w.x & 0xffffu);
-    q.status = static_cast<int16_t>(w.x >> 16);
-    const int tt = static_cast<int>(w.y);
-    q.t = kind == CCMPC_REC_KIND_AFFINE_COMPACT ? tt : (tt >> 16);
-  }
-  return q;
-}
-__device__ __forceinline__ bool audit_rec_valid(const AuditRec &q, int T) {
-  return q.status == 0 && q.t >= 0 && q.t < T;
-}
 
 __device__ __forceinline__ void add_i64(int64_t *p, int64_t v) {
   atomicAdd(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v));
@@ -268,8 +208,7 @@ __global__ __launch_bounds__(kAuditThreads) void audit_kernel(AuditArgs a) {
 #pragma unroll
         for (int j = 0; j < W; ++j) {
           const double s = q.x * px[j] + q.y * py[j];
-          const double v = q.z - s;
-          const bool p = v >= 0.0 && v * v >= q.w;
+          const bool p = audit_protects(q.z - s, q.w);
           prot[j] = prot[j] || p;
           no += __popcll(__ballot(valid[j] && !p));
         }

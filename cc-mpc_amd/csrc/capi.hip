@@ -3,6 +3,7 @@
 
 #include "audit.hpp"
 #include "ccmpc_common.hpp"
+#include "quantile.hpp"
 
 namespace ccmpc {
 static thread_local std::string g_last_error;
@@ -269,6 +270,59 @@ extern "C" int ccmpc_risk_audit(const void *positions, int dtype, int64_t ld, in
                            static_cast<const unsigned char *>(rec), rec_kind, P, R * R,
                            out_hit, out_hit_any, out_min_d2, out_rec_open, out_open};
   const int rc = ccmpc::launch_risk_audit(a, ccmpc::as_stream(stream));
+  CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
+  CCMPC_LAUNCH_CHECK();
+  return CCMPC_OK;
+}
+
+// ---- Monte-Carlo calibration of the offsets (quantile.hip) ----------------------------------
+extern "C" size_t ccmpc_risk_quantile_workspace_bytes(int64_t T, int rec_kind, int64_t n_cells) {
+  if (T < 1 || T > ccmpc::kAuditMaxT || n_cells < 0 || n_cells >= (1 << 30)) return 0;
+  const int P = ccmpc::audit_rows(rec_kind, T);
+  if (P < 0) return 0;
+  return ccmpc::quantile_workspace_bytes(n_cells, P);
+}
+
+extern "C" int ccmpc_risk_quantile(const void *positions, int dtype, int64_t ld, int64_t T,
+                                   const double *origin, const int64_t *cell_off,
+                                   const int64_t *cell_cnt, int64_t n_cells,
+                                   int64_t n_particles_bound, const void *rec, int rec_kind,
+                                   double R, const int64_t *cell_allow, void *workspace,
+                                   size_t workspace_bytes, double *out_q, double *out_rhs,
+                                   int32_t *out_status, ccmpc_stream_t stream) {
+  CCMPC_REQUIRE(T >= 1 && T <= ccmpc::kAuditMaxT, "T must be in [1, 40]");
+  CCMPC_REQUIRE(std::isfinite(R) && R > 0.0, "R must be finite and positive");
+  const int P = ccmpc::audit_rows(rec_kind, T);
+  CCMPC_REQUIRE(P >= 0, "unknown rec_kind");
+  CCMPC_REQUIRE(n_cells >= 0 && n_cells < (1 << 30), "bad n_cells");
+  CCMPC_REQUIRE(n_particles_bound >= 0 && n_particles_bound < (int64_t(1) << 32),
+                "n_particles_bound must be in [0, 2^32)");
+  CCMPC_REQUIRE(dtype == CCMPC_F64 || dtype == CCMPC_F32, "bad dtype");
+  CCMPC_REQUIRE(ld % 4 == 0 && ld > 0, "ld must be a positive multiple of 4");
+  // P == 0 (T = 1 of the half-space kinds): no rows, nothing is written
+  CCMPC_REQUIRE(P == 0 || (out_q && out_rhs && out_status), "null output");
+  if (workspace_bytes < ccmpc::quantile_workspace_bytes(n_cells, P)) {
+    ccmpc::set_error("ccmpc_risk_quantile: workspace too small");
+    return CCMPC_ERR_ARG;
+  }
+  if (n_cells == 0 || P == 0) return CCMPC_OK;
+  CCMPC_REQUIRE(positions && cell_off && cell_cnt && rec && workspace, "null pointer");
+  CCMPC_REQUIRE(ccmpc::aligned(positions, 16) && ccmpc::aligned(rec, 16) &&
+                    ccmpc::aligned(workspace, 16),
+                "positions, records and workspace must be 16-byte aligned");
+  CCMPC_REQUIRE(ccmpc::aligned(out_q, 8) && ccmpc::aligned(out_rhs, 8) &&
+                    ccmpc::aligned(out_status, 4) && ccmpc::aligned(cell_allow, 8),
+                "outputs must be 8-byte (status 4-byte) aligned");
+  const size_t CP = static_cast<size_t>(n_cells) * static_cast<size_t>(P);
+  unsigned char *ws = static_cast<unsigned char *>(workspace);
+  ccmpc::QuantArgs a{positions, dtype, ld, static_cast<int>(T), origin, cell_off, cell_cnt,
+                     static_cast<int>(n_cells), n_particles_bound,
+                     static_cast<const unsigned char *>(rec), rec_kind, P, R * R, cell_allow,
+                     reinterpret_cast<ccmpc::QuantRec *>(ws),
+                     reinterpret_cast<uint32_t *>(ws + CP * sizeof(ccmpc::QuantRec)),
+                     reinterpret_cast<int64_t *>(ws + CP * (sizeof(ccmpc::QuantRec) + 1024)),
+                     out_q, out_rhs, out_status};
+  const int rc = ccmpc::launch_risk_quantile(a, ccmpc::as_stream(stream));
   CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
   CCMPC_LAUNCH_CHECK();
   return CCMPC_OK;

@@ -1,0 +1,54 @@
+// Monte-Carlo calibration of half-space offsets to a risk budget: an exact batched selection on
+// the particle store (quantile.hip); the C entry point with its argument checks is
+// ccmpc_risk_quantile in capi.hip.
+#pragma once
+#include "audit.hpp"
+
+namespace ccmpc {
+
+constexpr int kQuantDigits = 8;     // 8-bit digits of the 64-bit key, most significant first
+constexpr int kQuantMaxChunk = 32;  // records per counting workgroup: 1 KiB of LDS bins each
+
+// A record as the counting passes read it (written by the call's first launch, its prefix
+// extended by every narrowing launch).  t < 0: nothing to select (VACUOUS or SKIPPED); else the
+// step in the low byte and the selection state above it (quantile.hip).
+struct QuantRec {
+  double n0, n1;
+  uint64_t prefix;  // the digits of q's key found so far
+  int32_t side, t;
+};
+static_assert(sizeof(QuantRec) == 32, "QuantRec is read as two 16-byte loads");
+
+// Workspace: [C P] QuantRec, [C P][256] bins (uint32), [C P] remaining ranks (int64).
+constexpr size_t kQuantBytesPerRec = sizeof(QuantRec) + sizeof(int64_t) + 256 * sizeof(uint32_t);
+inline size_t quantile_workspace_bytes(int64_t n_cells, int P) {
+  return static_cast<size_t>(n_cells) * static_cast<size_t>(P) * kQuantBytesPerRec + 64;
+}
+
+struct QuantArgs {
+  const void *pos;
+  int dtype;
+  int64_t ld;
+  int T;
+  const double *origin;
+  const int64_t *off, *cnt;
+  int n_cells;
+  int64_t n_bound;
+  const unsigned char *rec;  // [n_cells][P] records of `kind`
+  int kind, P;
+  double R2;                 // R * R
+  const int64_t *allow;      // [n_cells] or null: zeros
+  QuantRec *qrec;            // workspace
+  uint32_t *bins;
+  int64_t *rank;
+  double *out_q, *out_rhs;
+  int32_t *out_status;
+};
+
+// 1 + 2 * kQuantDigits launches on `s`: the initial values, then per digit a counting pass over
+// the store and the narrowing of every record's prefix (the last one writes the outputs).  The
+// sequence depends on (T, kind, n_cells, n_bound) only.  CCMPC_OK or CCMPC_ERR_ARG when a grid
+// would not fit.  No allocation, no synchronisation.
+int launch_risk_quantile(const QuantArgs &a, hipStream_t s);
+
+}  // namespace ccmpc

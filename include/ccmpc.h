@@ -696,6 +696,66 @@ int ccmpc_risk_audit(const void *positions, int dtype, int64_t ld, int64_t T,
                      int64_t *out_rec_open, int64_t *out_open, ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Monte-Carlo calibration of half-space offsets to a risk budget: which offset would leave at
+ * most cell_allow[c] particles of the cell open?  The companion of ccmpc_risk_audit (no
+ * reference counterpart): an exact batched selection, one order statistic per record, on the
+ * planes the audit streams.  Store arguments (positions .. n_particles_bound), rec / rec_kind,
+ * R and the fields read of a record (n0, n1, rhs, side, status, its step t) are the audit's,
+ * with the same F32 rule (double)rel + origin[c]; P = T(T-1)/2 (half-space kinds) or T.
+ *  cell_allow[c]   device int64, NULL = all zeros: the number m of particles of cell c a
+ *                  record may leave open (e.g. floor(eps_ura / ph * N_c))
+ *
+ * All arithmetic is float64, in the stated order, with no contraction.  A record is calibrated
+ * when status == 0, 0 <= t < T, and n0 and n1 are finite and not both non-finite.  For a
+ * calibrated record of cell c take N = cell_cnt[c] and m = cell_allow[c]; a negative m is an
+ * argument error, detected on the device and reported per record as SKIPPED (the call never
+ * reads device memory on the host).
+ *  Projection of particle i: s_i = n0*px + n1*py (the audit's s, from the world position at
+ *  step t), w_i = side*s_i + 0.0 (the + 0.0 makes -0 a +0, so bit order equals value order).
+ *  out_q[c][P]      when m < N: the (m+1)-th largest w_i, i.e. the element at index N-1-m of the
+ *                   ascending sort.  Its bits are exact: each w_i is two products and one sum,
+ *                   no evaluation order can change it.
+ *  out_rhs[c][P]    side*u*, where u* is the smallest double u for which the audit's own
+ *                   predicate protects a particle with s = side*q under rhs = side*u:
+ *                     v = side*(rhs - s);  v >= 0 && v*v >= (R*R)*(n0*n0 + n1*n1)
+ *                   The predicate is monotone in u, so u* is unique and the output is
+ *                   bit-comparable (+inf where no double satisfies it).
+ *  out_status[c][P] int32: 0 calibrated;
+ *                   CCMPC_CAL_VACUOUS: m >= N, empty cells included -- nothing needs
+ *                   protecting: out_q = -inf, out_rhs = the record's own rhs, copied;
+ *                   CCMPC_CAL_SKIPPED: the record is not calibrated: out_q = NaN, out_rhs =
+ *                   the record's own rhs.
+ * Consequences: feed the record back to ccmpc_risk_audit with rhs replaced by out_rhs.  Every
+ * particle with w_i <= q is then protected, so its rec_open is at most #{i : w_i > q} <= m --
+ * exactly that number unless some w_i > q lies within the rounding of u* - q.  With u* moved
+ * one ulp towards the particles, rec_open is >= #{w_i >= q} > m.
+ * Positions are assumed finite; non-finite projections give unspecified values but no
+ * out-of-range access.
+ *
+ * CCMPC_ERR_ARG: T outside [1, 40], R not finite or <= 0, an unknown rec_kind, ld not a
+ * multiple of 4, a NULL output (none is needed where P == 0: T = 1 of the half-space kinds,
+ * where the call writes nothing), a workspace smaller than
+ * ccmpc_risk_quantile_workspace_bytes(T, rec_kind, n_cells) (which returns 0 for arguments the
+ * call rejects) or not 16-byte aligned, n_particles_bound >= 2^32 (counts are 32-bit).
+ * The call is capturable: it never synchronises, never reads device memory on the host, and
+ * needs neither an initialised workspace nor initialised outputs (its first launch writes the
+ * initial values).  The launch sequence is fixed by (T, rec_kind, n_cells, n_particles_bound):
+ * the first launch, then 8 x (a counting pass over the store, a narrowing launch); a radix
+ * select on the order-preserving 64-bit key of w, 8 bits per pass.  Integer atomics only: no
+ * output bit depends on execution order.  Do not share one workspace between concurrent
+ * streams.
+ * ------------------------------------------------------------------------------------- */
+#define CCMPC_CAL_VACUOUS 1
+#define CCMPC_CAL_SKIPPED 2
+size_t ccmpc_risk_quantile_workspace_bytes(int64_t T, int rec_kind, int64_t n_cells);
+int ccmpc_risk_quantile(const void *positions, int dtype, int64_t ld, int64_t T,
+                        const double *origin, const int64_t *cell_off, const int64_t *cell_cnt,
+                        int64_t n_cells, int64_t n_particles_bound, const void *rec,
+                        int rec_kind, double R, const int64_t *cell_allow, void *workspace,
+                        size_t workspace_bytes, double *out_q, double *out_rhs,
+                        int32_t *out_status, ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * TEST ONLY (not a reference interface): the half-space tail's device functions -- the ones
  * ccmpc_minkowski_cycle / ccmpc_minkowski / ccmpc_affine_scale run per record -- on n batched
  * inputs, so the reference's component golden vectors reach the device arithmetic.  Device
