@@ -140,10 +140,24 @@ __device__ __forceinline__ M2 block(const double *cov, int rows, int i, int j) {
   return {p[0], p[1], p[rows], p[rows + 1]};
 }
 
+// Pair index p -> (t, tau), tau < t, p = t (t - 1) / 2 + tau.  For p < 2^20 the float estimate
+// is within one of t (1 + 8 p < 2^23 + 1 is exact in float, a correctly rounded square root is
+// exact at the squares (2 t - 1)^2 and the next row's start is >= 4 / (2 t + 1) > 5 ulp away),
+// so one select-based correction is exact; two data-dependent while loops here compiled to
+// exec-mask loops at the head of every record's chain (C2 bench step 8.93 us with the loops,
+// 8.85 without, profiles/r11).  Build knob (0: the loops).
+#ifndef CCMPC_PAIR_CLOSED
+#define CCMPC_PAIR_CLOSED 1
+#endif
 __device__ __forceinline__ void pair_of(int p, int &t, int &tau) {
   int tt = static_cast<int>((1.0f + sqrtf(1.0f + 8.0f * static_cast<float>(p))) * 0.5f);
+#if CCMPC_PAIR_CLOSED
+  const int lo = tt * (tt - 1) / 2;  // row tt holds p in [lo, lo + tt)
+  tt += lo > p ? -1 : (lo + tt <= p ? 1 : 0);
+#else
   while (tt * (tt - 1) / 2 > p) --tt;
   while ((tt + 1) * tt / 2 <= p) ++tt;
+#endif
   t = tt;
   tau = p - tt * (tt - 1) / 2;
 }
@@ -310,7 +324,8 @@ __device__ void minkowski_pair(const double *C, const double *mu, const double *
   *reinterpret_cast<int4 *>(&out->which) = make_int4(which, side, status, (t << 16) | tau);
 }
 
-// All pairs of one cell by the threads [0, nthreads) of the calling group, with the cell's
+// All pairs of one cell by the threads [0, NTH) of the calling group (NTH: the kernel's
+// compile-time workgroup size, never blockDim.x -- see gram.hpp), with the cell's
 // reference trajectory `ref` ([T][2]) and risk constants already at hand; lb_s has room for
 // T(T-1)/2 doubles.  The record of a pair is a serial chain (two MVOE fixed points, then the
 // tangent) on one lane; its lower bound does not depend on that chain, so with >= 2 waves the
@@ -318,9 +333,11 @@ __device__ void minkowski_pair(const double *C, const double *mu, const double *
 // and write their record field themselves.  Up to 128 pairs that lower-bound wave also takes
 // the per-t minimum (no workgroup barrier: callers must not rely on one after this call); past
 // that, the barrier needed before the per-t minimum is included.
+template <int NTH>
 __device__ void minkowski_cell(const double *C, const double *mu, int T, int cell,
                                const double *ref, double chi_r, double chi_p, double gamma,
-                               const MinkParams &mp, double *lb_s, int tid, int nthreads) {
+                               const MinkParams &mp, double *lb_s, int tid) {
+  constexpr int nthreads = NTH;
   const int rows = 2 * T;
   const int P = T * (T - 1) / 2;
   ccmpc_halfspace *rec = mp.out_rec + static_cast<int64_t>(cell) * P;
@@ -381,12 +398,13 @@ __device__ void minkowski_cell(const double *C, const double *mu, int T, int cel
 }
 
 // Same, reading the reference trajectory and risk constants from global memory.
+template <int NTH>
 __device__ void minkowski_cell(const double *C, const double *mu, int T, int cell,
-                               const MinkParams &mp, double *lb_s, int tid, int nthreads) {
+                               const MinkParams &mp, double *lb_s, int tid) {
   const int rsel = mp.cell_ref ? mp.cell_ref[cell] : 0;
   const double *ref = mp.ref_traj + static_cast<int64_t>(rsel) * (2 * T);
-  minkowski_cell(C, mu, T, cell, ref, mp.cell_risk[3 * cell + 0], mp.cell_risk[3 * cell + 1],
-                 mp.cell_risk[3 * cell + 2], mp, lb_s, tid, nthreads);
+  minkowski_cell<NTH>(C, mu, T, cell, ref, mp.cell_risk[3 * cell + 0],
+                      mp.cell_risk[3 * cell + 1], mp.cell_risk[3 * cell + 2], mp, lb_s, tid);
 }
 
 // The unfused half-space launch (constraints.hip): one wave per (cell, t), lanes = the row's pairs.

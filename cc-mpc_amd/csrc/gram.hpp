@@ -46,6 +46,8 @@ inline int row_blocks(int64_t T) { return static_cast<int>((2 * T + 15) / 16); }
 template <int RB>
 struct Geo {
   static constexpr int NW = RB == 1 ? (1 << CCMPC_LG_NW1) : (RB <= 2 ? 4 : (1 << CCMPC_LG_NW_BIG));
+  // the workgroup size: the kernel's launch bound, its helpers' NTH and the host's block size
+  static constexpr int THREADS = NW * 64;
   static constexpr int S = RB == 1 ? 4 : (RB == 2 ? 2 : 1);
   static constexpr int NACC = (n_tiles(RB) == 1) ? 2 : 1;  // 2 chains when there is one tile
   static constexpr int MIN_WAVES_PER_SIMD = RB == 1 ? 4 : (RB <= 2 ? 2 : CCMPC_MINW_BIG);
@@ -499,6 +501,14 @@ __host__ __device__ constexpr int combine_xch_doubles(int rb, int nw) {
   return nw * combine_tiles_per_round(rb) * 256 + 64 * rb * nw;
 }
 
+// NTH, the workgroup's thread count, is a template parameter of every helper below that strides
+// by it (combine_waves and combine4 take it from NW; tree_climb, gather_root, finalize_cell and
+// minkowski_cell are given it), from the same constant as the kernel's __launch_bounds__ and the
+// host's block size.  blockDim.x is NOT a compile-time value under __launch_bounds__: each use
+// is a load from the hidden kernel arguments (a scalar load of the block count, a compare, a
+// 16-bit vector load of the group size or the remainder, a full wait) -- a cold line of the
+// argument segment and two dependent round trips on the last arriver's path.
+//
 // Combine the NW waves' accumulators in a fixed order (wave 0 + 1 + ... + NW-1) and write the
 // item's slab: to global memory write-through (to_lds = false) or to the LDS slab `dst`
 // (to_lds = true).  Rounds of up to combine_tiles_per_round tiles: every wave parks its tiles
@@ -514,6 +524,7 @@ __device__ __forceinline__ void combine_waves(const d4 (&acc)[NACC][n_tiles(RB)]
   constexpr int NT = n_tiles(RB);
   constexpr int TB = combine_tiles_per_round(RB);
   constexpr int XR = NW * TB * 256;  // the row sums' park area: [w][RB * 16]
+  constexpr int NTH = NW * 64;       // the workgroup's threads (never blockDim.x: see NTH above)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const __amdgpu_buffer_rsrc_t rs = slab_rsrc(dst);
   // the row sums ride the first round: every lane parks its partial (lane r + 16 g: row r of
@@ -537,7 +548,7 @@ __device__ __forceinline__ void combine_waves(const d4 (&acc)[NACC][n_tiles(RB)]
     __syncthreads();
     // slab entry t*256 + 4 l + k <-> (tile t, lane l, register k); pairs (k, k+1), k even
     const int n_e = (NT - t0 < TB ? NT - t0 : TB) * 256;
-    for (int e = 2 * threadIdx.x; e < n_e; e += 2 * blockDim.x) {
+    for (int e = 2 * threadIdx.x; e < n_e; e += 2 * NTH) {
       const int tb = e >> 8, l = (e >> 2) & 63, k = e & 3;
       const double *x = xch + (tb * 4 + k) * 64 + l;
       double a = x[0], b = x[64];
@@ -556,7 +567,7 @@ __device__ __forceinline__ void combine_waves(const d4 (&acc)[NACC][n_tiles(RB)]
     }
     if (t0 == 0) {
       // row-sum pair (2 i, 2 i + 1) of row block b: wave 0's value, then + waves 1, 2, ...
-      const int i = static_cast<int>(blockDim.x) - 1 - static_cast<int>(threadIdx.x);
+      const int i = NTH - 1 - static_cast<int>(threadIdx.x);
       if (i < 8 * RB) {
         const int b = i >> 3, r = 2 * (i & 7);
         auto rowsum = [&](int o, int rr) {  // wave o's row rr: ((g0 + g1) + (g2 + g3))
@@ -748,7 +759,7 @@ __device__ __forceinline__ double2 sum_group2(const double *__restrict__ slab0, 
 // Climb the tree from a published leaf.  Returns true in the workgroup that must finalise the
 // cell; then *root points at the root level's first slab and *root_n is its node count
 // (<= kRootFanIn).  first0 is the cell's first item; deeper levels follow tree_next_first.
-template <int E>
+template <int E, int NTH>
 __device__ bool tree_climb(const TreeLayout &L, int32_t idx, int32_t nit, int32_t first0,
                            int cell, int *flag, const double **root, int32_t *root_n) {
   int32_t n_l = nit, first_l = first0;
@@ -767,7 +778,7 @@ __device__ bool tree_climb(const TreeLayout &L, int32_t idx, int32_t nit, int32_
     }
     double *parent = L.slabs[l + 1] + static_cast<int64_t>(first_up + grp) * E;
     const __amdgpu_buffer_rsrc_t rp = slab_rsrc(parent);
-    for (int e = 2 * threadIdx.x; e < E; e += 2 * blockDim.x) {
+    for (int e = 2 * threadIdx.x; e < E; e += 2 * NTH) {
       const double2 s = sum_group2(children, gsize, E, e);
       st2_sc1(rp, 8 * e, s.x, s.y);
     }
@@ -884,7 +895,7 @@ __device__ __forceinline__ void combine4(const double (&acc)[n_pairs(NB)], const
   }
   __syncthreads();
   const __amdgpu_buffer_rsrc_t rs = slab_rsrc(dst);
-  for (int e = 2 * threadIdx.x; e < Sch::E; e += 2 * blockDim.x) {
+  for (int e = 2 * threadIdx.x; e < Sch::E; e += 2 * NW * 64) {
     double a = 0.0, b = 0.0;
     if (e < Sch::GRAM) {
 #pragma unroll
@@ -995,13 +1006,14 @@ __host__ __device__ constexpr int gather_part_doubles(int E) {
 //    lanes l and l + 32 of one wave and meet by a cross-lane move, G0 + G1 in the lower lane:
 //    no LDS meeting point, one barrier less, the same bits.
 // The branch on root_n is workgroup-uniform.  Ends with a barrier.
-template <typename Sch>
+template <typename Sch, int NTH>
 __device__ __forceinline__ void gather_root(const double *__restrict__ root, int32_t root_n,
                                             int rows, double *dst_lds, double *part_lds) {
   constexpr int E = Sch::E, GRAM = Sch::GRAM, H = Sch::GRAM / 2;
   constexpr int HP = (H + 63) / 64 * 64;  // a group's slots, padded to whole waves
   constexpr bool kAllPairs = CCMPC_SPREAD_ALL_PAIRS && GRAM <= 256;  // T <= 10
-  const int tid = threadIdx.x, nth = blockDim.x;
+  constexpr int nth = NTH;
+  const int tid = threadIdx.x;
   if (root_n <= kFanIn || root_n > kRootFanIn || !part_lds) {
     // (a root wider than kRootFanIn exists only at the tree's depth bound; it, and a caller
     // with no LDS for the groups, passing part_lds = nullptr, go group by group in each thread)
@@ -1087,14 +1099,15 @@ __device__ __forceinline__ void gather_root(const double *__restrict__ root, int
 // shift_lds.  Writes cov to global memory and, when cov_lds != nullptr, to LDS as well (row
 // stride 2T) for the fused half-space tail.  Called by every thread of the workgroup; ends
 // with a barrier.
-template <typename Sch, typename Reader>
+template <typename Sch, int NTH, typename Reader>
 __device__ void finalize_cell(Reader rd, int64_t cnt, int T, const double *shift_lds,
                               double *S_lds, double o0, double o1, double *__restrict__ mean,
                               double *__restrict__ cov, double *mean_lds, double *cov_lds,
                               const double *S_in = nullptr) {
   constexpr int GRAM = Sch::GRAM;
   constexpr int D = Sch::D;
-  const int tid = threadIdx.x, nth = blockDim.x;
+  constexpr int nth = NTH;
+  const int tid = threadIdx.x;
   const int rows = 2 * T;
   const double n = static_cast<double>(cnt);
   // rd(e) returns the summed entry pair (e, e+1), e even.  S_in: the summed row sums already in

@@ -268,7 +268,7 @@ struct EpilogueLds {
   int *flag;
 };
 
-template <typename Sch, bool MINK, bool COV_IN_LDS, bool DEFER, typename Publish>
+template <typename Sch, int NTH, bool MINK, bool COV_IN_LDS, bool DEFER, typename Publish>
 __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &loc, int32_t nit,
                                               int T, const TreeLayout &tree,
                                               const double *__restrict__ origin,
@@ -292,20 +292,20 @@ __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &lo
     if (DEFER && nit <= kRootFanIn) return;
     const double *root;
     int32_t root_n;
-    const bool last = tree_climb<E>(tree, loc.chunk_idx, nit, loc.first, cell, L.flag, &root,
-                                    &root_n);
+    const bool last = tree_climb<E, NTH>(tree, loc.chunk_idx, nit, loc.first, cell, L.flag,
+                                         &root, &root_n);
     PROBE_TS(4);
     if (!last) return;
-    gather_root<Sch>(root, root_n, rows, L.slab, L.cov);  // the exchange buffer is free here
+    gather_root<Sch, NTH>(root, root_n, rows, L.slab, L.cov);  // the exchange buffer is free here
     PROBE_GATHERED();
   }
-  finalize_cell<Sch>([&](int e) { return double2{L.slab[e], L.slab[e + 1]}; }, loc.cnt, T,
-                     L.shift, L.S, o0, o1, mean, cov, L.mean, COV_IN_LDS ? L.cov : nullptr,
-                     L.slab + Sch::GRAM);
+  finalize_cell<Sch, NTH>([&](int e) { return double2{L.slab[e], L.slab[e + 1]}; }, loc.cnt, T,
+                          L.shift, L.S, o0, o1, mean, cov, L.mean, COV_IN_LDS ? L.cov : nullptr,
+                          L.slab + Sch::GRAM);
   PROBE_TS(5);
   if (MINK)
-    minkowski_cell(COV_IN_LDS ? L.cov : cov, L.mean, T, cell, L.ref, L.ref[rows],
-                   L.ref[rows + 1], L.ref[rows + 2], mp, L.lb, threadIdx.x, blockDim.x);
+    minkowski_cell<NTH>(COV_IN_LDS ? L.cov : cov, L.mean, T, cell, L.ref, L.ref[rows],
+                        L.ref[rows + 1], L.ref[rows + 2], mp, L.lb, threadIdx.x);
   PROBE_TS(6);
 }
 
@@ -334,7 +334,10 @@ __device__ __forceinline__ WaveRange wave_range(int64_t a, int64_t b, int w, int
 }
 
 // The per-cell inputs of the half-space tail: issued at an item's start, landing behind its
-// stream loop (thread i < 2T: ref_traj row, then the 3 risk constants).
+// stream loop (thread i < 2T: ref_traj row, then the 3 risk constants).  (The two guarded loads
+// share a result register, so the compiler waits for the first before it issues the second --
+// a vmcnt(0) in wave 0 ahead of its particle loads.  One load from a selected address removes
+// that wait and was measured: no gain, bench step 8.84 against 8.83 us, profiles/r11.)
 __device__ __forceinline__ double prefetch_tail(const MinkParams &mp, const ItemLoc &loc,
                                                 int rows) {
   if (threadIdx.x < rows) return mp.ref_traj[static_cast<int64_t>(loc.ref_sel) * rows + threadIdx.x];
@@ -344,7 +347,7 @@ __device__ __forceinline__ double prefetch_tail(const MinkParams &mp, const Item
 
 template <typename P, int RB, bool MINK, bool BAL>
 // The fused half-space tail needs a few more registers than the 128 of 4 waves/SIMD at RB = 1.
-__global__ __launch_bounds__(Geo<RB>::NW * 64,
+__global__ __launch_bounds__(Geo<RB>::THREADS,
                              (MINK && RB == 1) ? 3 : Geo<RB>::MIN_WAVES_PER_SIMD)
 void moments_kernel(
     const int64_t *__restrict__ cell_cnt, const int64_t *__restrict__ cell_off,
@@ -457,7 +460,7 @@ void moments_kernel(
       if (w == 0 && g == 0) shift_lds[16 * bb + r] = sh[bb];
     }
     const EpilogueLds L{slab_lds, shift_lds, S_lds, mean_lds, xch, lb_s, ref_lds, &flag};
-    cell_epilogue<Scheme16<RB>, MINK, COV_IN_LDS, DEFER>(
+    cell_epilogue<Scheme16<RB>, G::THREADS, MINK, COV_IN_LDS, DEFER>(
         [&](double *dst, bool to_lds) {
           combine_waves<RB, NACC, G::NW>(acc, s1, xch, dst, to_lds);
         },
@@ -619,6 +622,8 @@ __device__ __forceinline__ void mfma_group4(const typename Row4<P>::type (&loade
 #define CCMPC_NW4 4
 #endif
 constexpr int kNW4 = CCMPC_NW4;
+// the Scheme4 kernel's workgroup size: its launch bound, its helpers' NTH, the host's block size
+constexpr int kThreads4 = kNW4 * 64;
 #ifndef CCMPC_M4_OCC  // Scheme4 workgroups per CU the register budget must allow (build knob)
 #define CCMPC_M4_OCC(NB) (((NB) <= 5 ? 3 : 2) * 4 / kNW4 > 0 ? ((NB) <= 5 ? 3 : 2) * 4 / kNW4 : 1)
 #endif
@@ -631,7 +636,7 @@ constexpr int m4_occ(int nb) {
 }
 
 template <typename P, int NB, bool MINK, bool BAL>
-__global__ __launch_bounds__(kNW4 * 64, m4_occ<P>(NB)) void moments4_kernel(
+__global__ __launch_bounds__(kThreads4, m4_occ<P>(NB)) void moments4_kernel(
     const int64_t *__restrict__ cell_cnt, const int64_t *__restrict__ cell_off,
     const int32_t *__restrict__ cell_ref, int n_cells, const P *__restrict__ pos, int64_t ld,
     int T, const double *__restrict__ origin, int lg_wq, TreeLayout tree,
@@ -719,7 +724,7 @@ __global__ __launch_bounds__(kNW4 * 64, m4_occ<P>(NB)) void moments4_kernel(
     static_assert(kNW4 * Combine4Layout<NB>::XS >= gather_part_doubles(E),
                   "xch must hold the root gather's group slabs");
     const EpilogueLds L{slab_lds, shift_lds, S_lds, mean_lds, xch, lb_s, ref_lds, &flag};
-    cell_epilogue<Sch, MINK, MINK, false>(
+    cell_epilogue<Sch, kThreads4, MINK, MINK, false>(
         [&](double *dst, bool to_lds) { combine4<NB, kNW4>(acc, s1, xch, dst, to_lds); }, loc,
         nit, T, tree, origin, out_mean, out_cov, mp, L);
   };
@@ -892,7 +897,7 @@ template <typename P, int RB, bool MINK>
 static int launch(const P *pos, int64_t ld, int T, const double *origin, const int64_t *off,
                   const int64_t *cnt, int n_cells, int64_t n_bound, void *ws, size_t ws_bytes,
                   double *mean, double *cov, const MinkParams &mp, hipStream_t s) {
-  constexpr int threads = Geo<RB>::NW * 64;
+  constexpr int threads = Geo<RB>::THREADS;
   const int lg_wq = store_lg_wave_quota(RB, n_bound);
   TreeLayout tree;
   const int grid =
@@ -922,7 +927,7 @@ template <typename P, int NB, bool MINK>
 static int launch4(const P *pos, int64_t ld, int T, const double *origin, const int64_t *off,
                    const int64_t *cnt, int n_cells, int64_t n_bound, void *ws, size_t ws_bytes,
                    double *mean, double *cov, const MinkParams &mp, hipStream_t s) {
-  constexpr int threads = kNW4 * 64;
+  constexpr int threads = kThreads4;
   const int lg_wq = store_lg_wave_quota(1, n_bound);
   TreeLayout tree;
   const int grid =

@@ -162,9 +162,11 @@ constexpr int kStageStride = 66;  // doubles per LDS row: bank-conflict-free bot
 __host__ __device__ constexpr int ideal_waves(int rb) {
   return rb == 1 ? CCMPC_IDEAL_WAVES1 : rb <= 2 ? 4 : 2;
 }
+// the fused kernel's workgroup size: its launch bound, its helpers' NTH and the host's block size
+__host__ __device__ constexpr int ideal_threads(int rb) { return 64 * ideal_waves(rb); }
 
 template <int RB, bool MINK>
-__global__ __launch_bounds__(64 * ideal_waves(RB)) void ideal_gram_kernel(
+__global__ __launch_bounds__(ideal_threads(RB)) void ideal_gram_kernel(
     const double *__restrict__ prev_mean, const double *__restrict__ prev_cov, int T_src,
     const int32_t *__restrict__ src_cell, int T, int64_t n, int64_t chunk, int64_t items_per_cell,
     const double *__restrict__ x0, uint64_t seed_arg, const uint64_t *__restrict__ seed_dev,
@@ -176,6 +178,7 @@ __global__ __launch_bounds__(64 * ideal_waves(RB)) void ideal_gram_kernel(
   constexpr int D = 16 * RB;
   constexpr int E = slab_doubles(RB);
   constexpr int NW = ideal_waves(RB);
+  constexpr int NTH = ideal_threads(RB);
 #if CCMPC_IDEAL_LDS_SHRINK
   __shared__ StepPlan plan[8 * RB];
 #else
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(64 * ideal_waves(RB)) void ideal_gram_kernel(
   const uint32_t rng = rng_cell ? static_cast<uint32_t>(rng_cell[cell]) : static_cast<uint32_t>(cell);
   if (threadIdx.x == 0) status_s = 0;
   __syncthreads();
-  for (int t = threadIdx.x; t < T; t += blockDim.x) {
+  for (int t = threadIdx.x; t < T; t += NTH) {
     const int st = build_step(mu, cv, rows_src, t, plan[t]);
     if (st) atomicMin(&status_s, st);
   }
@@ -286,8 +289,8 @@ __global__ __launch_bounds__(64 * ideal_waves(RB)) void ideal_gram_kernel(
   combine_waves<RB, 1, NW>(acc, s1, xch, tree.slabs[0] + item * E, false);
   const double *root;
   int32_t root_n;
-  if (!tree_climb<E>(tree, static_cast<int32_t>(cidx), static_cast<int32_t>(items_per_cell),
-                     static_cast<int32_t>(cell * items_per_cell), cell, &flag, &root, &root_n))
+  if (!tree_climb<E, NTH>(tree, static_cast<int32_t>(cidx), static_cast<int32_t>(items_per_cell),
+                          static_cast<int32_t>(cell * items_per_cell), cell, &flag, &root, &root_n))
     return;
   double *mean = out_mean + static_cast<int64_t>(cell) * rows;
   double *cov = out_cov + static_cast<int64_t>(cell) * rows * rows;
@@ -295,10 +298,12 @@ __global__ __launch_bounds__(64 * ideal_waves(RB)) void ideal_gram_kernel(
   // the sample stage is free after combine_waves: the root slab, then (where they fit: T <= 24)
   // the gather's group slabs
   constexpr bool kParts = NW * D * kStageStride >= E + gather_part_doubles(E);
-  gather_root<Scheme16<RB>>(root, root_n, rows, stage_all, kParts ? stage_all + E : nullptr);
-  finalize_cell<Scheme16<RB>>([&](int e) { return double2{stage_all[e], stage_all[e + 1]}; }, n, T,
-                    shift_s, S_lds, 0.0, 0.0, mean, cov, mean_lds, nullptr);
-  if (MINK) minkowski_cell(cov, mean_lds, T, cell, mp, lb_s, threadIdx.x, blockDim.x);
+  gather_root<Scheme16<RB>, NTH>(root, root_n, rows, stage_all,
+                                 kParts ? stage_all + E : nullptr);
+  finalize_cell<Scheme16<RB>, NTH>(
+      [&](int e) { return double2{stage_all[e], stage_all[e + 1]}; }, n, T, shift_s, S_lds, 0.0,
+      0.0, mean, cov, mean_lds, nullptr);
+  if (MINK) minkowski_cell<NTH>(cov, mean_lds, T, cell, mp, lb_s, threadIdx.x);
 }
 
 // samples per work item (multiple of 256 = 4 waves x 64): ~CCMPC_IDEAL_ITEMS items per launch
@@ -324,7 +329,7 @@ static int launch_ideal_gram(const double *pm, const double *pc, int T_src, cons
   if (!tree_layout(ws, ws_bytes, ipc * n_cells, n_cells, slab_doubles(RB), tree))
     return CCMPC_ERR_WORKSPACE;
   hipLaunchKernelGGL((ideal_gram_kernel<RB, MINK>), dim3(static_cast<unsigned>(ipc * n_cells)),
-                     dim3(64 * ideal_waves(RB)), 0, s, pm, pc, T_src, src, T, n, chunk, ipc, x0,
+                     dim3(ideal_threads(RB)), 0, s, pm, pc, T_src, src, T, n, chunk, ipc, x0,
                      seed, seed_dev, rng, tree, out_mean, out_cov, status, mp);
   return CCMPC_OK;
 }

@@ -83,8 +83,9 @@ def main():
     lib.ccmpc_probe_timestamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
     jobs = [a.split(":") for a in sys.argv[1:]] or (
         [(n, "moments") for n in CONFIGS] + [("C2", "cycle")])
-    for name, what in jobs:
-        one(name, what, dev, lib, back_to_back=5)
+    for _ in range(int(os.environ.get("REPS", "1"))):  # REPS=n: n tables, to see their scatter
+        for name, what in jobs:
+            one(name, what, dev, lib, back_to_back=5)
 
 
 if __name__ == "__main__":
