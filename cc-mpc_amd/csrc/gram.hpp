@@ -1099,6 +1099,15 @@ __device__ __forceinline__ void gather_root(const double *__restrict__ root, int
 // shift_lds.  Writes cov to global memory and, when cov_lds != nullptr, to LDS as well (row
 // stride 2T) for the fused half-space tail.  Called by every thread of the workgroup; ends
 // with a barrier.
+// Build knob: while the Gram fits the workgroup (GRAM <= NTH: T <= 8 on 16-row tiles, T <= 10 on
+// 4-row blocks) thread e takes entry e alone, its half of the pair rd(e & ~1) returns, instead of
+// the pair (e, e + 1) in series with most of the workgroup idle at the barrier: a thread's second
+// entry waited for the first's divisions and, by the compiler's vmcnt wait in front of it, for
+// the first's stores.  Same values, same addresses.  C2 cycle 8.91 -> 8.66 us, the finaliser
+// 0.73 -> 0.48 on the phase stamps (profiles/r12).  Wider Grams keep the pair loop.
+#ifndef CCMPC_ONE_ENTRY
+#define CCMPC_ONE_ENTRY 1
+#endif
 template <typename Sch, int NTH, typename Reader>
 __device__ void finalize_cell(Reader rd, int64_t cnt, int T, const double *shift_lds,
                               double *S_lds, double o0, double o1, double *__restrict__ mean,
@@ -1127,21 +1136,32 @@ __device__ void finalize_cell(Reader rd, int64_t cnt, int T, const double *shift
     mean[r] = m;
     if (mean_lds) mean_lds[r] = m;
   }
-  for (int e = 2 * tid; e < GRAM; e += 2 * nth) {
-    const PairUse u = pair_use<Sch>(e, rows);  // one value per symmetric pair
-    if (!u.use0 && !u.use1) continue;
-    const double2 g = rd(e);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      if (!(h ? u.use1 : u.use0)) continue;
-      const int i = h ? u.i1 : u.i0, j = h ? u.j1 : u.j0;
-      const double c = ((h ? g.y : g.x) - S[i] * S[j] / n) / (n - 1.0);
-      cov[i * rows + j] = c;
-      cov[j * rows + i] = c;
-      if (cov_lds) {
-        cov_lds[i * rows + j] = c;
-        cov_lds[j * rows + i] = c;
+  auto entry = [&](double g, int i, int j) {
+    const double c = (g - S[i] * S[j] / n) / (n - 1.0);
+    cov[i * rows + j] = c;
+    cov[j * rows + i] = c;
+    if (cov_lds) {
+      cov_lds[i * rows + j] = c;
+      cov_lds[j * rows + i] = c;
+    }
+  };
+  if constexpr (CCMPC_ONE_ENTRY && GRAM <= NTH) {
+    if (tid < GRAM) {  // (the schemes' decode is defined below GRAM only)
+      int i, j;
+      Sch::decode(tid, i, j);
+      if (i < rows && j < rows && i <= j) {  // one value per symmetric pair
+        const double2 g = rd(tid & ~1);
+        entry((tid & 1) ? g.y : g.x, i, j);
       }
+    }
+  } else {
+    for (int e = 2 * tid; e < GRAM; e += 2 * nth) {
+      const PairUse u = pair_use<Sch>(e, rows);  // one value per symmetric pair
+      if (!u.use0 && !u.use1) continue;
+      const double2 g = rd(e);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (h ? u.use1 : u.use0) entry(h ? g.y : g.x, h ? u.i1 : u.i0, h ? u.j1 : u.j0);
     }
   }
   __syncthreads();

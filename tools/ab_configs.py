@@ -15,7 +15,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = [("C2", 4, 5000, 8, 1), ("C3-1e3", 1, 1000, 8, 1), ("C3-2e4", 1, 20000, 8, 1),
            ("C3-1e5", 1, 100000, 8, 1), ("C4/8", 4, 20000, 12, 8), ("C4/1", 4, 20000, 12, 64),
-           ("C5", 8, 50000, 40, 1), ("C4/8-f32", 4, 20000, 12, 8), ("C4/1-f32", 4, 20000, 12, 64)]
+           ("C5", 8, 50000, 40, 1), ("C4/8-f32", 4, 20000, 12, 8), ("C4/1-f32", 4, 20000, 12, 64),
+           # C2's scene at T = 9 and 10: five 4-row blocks, a 240-entry Gram on 256 threads
+           ("C2-T9", 4, 5000, 9, 1), ("C2-T10", 4, 5000, 10, 1)]
 
 
 def child(only):

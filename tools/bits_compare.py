@@ -15,10 +15,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (name, O, N, T, scenes, store dtype): the C3 sweep (one cell per OV, up to 2-level trees),
-# C2, a Scheme4 single cell, the C4 batch and C5 (deferred root at T = 40)
+# C2, Scheme4 cells (T = 9, 10: a Gram narrower than the workgroup; T = 12), the C4 batch and
+# C5 (deferred root at T = 40)
 CONFIGS = [("C2", 4, 5000, 8, 1, "f32"), ("C3-1e3", 1, 1000, 8, 1, "f32"),
            ("C3-2e4", 1, 20000, 8, 1, "f32"), ("C3-1e5", 1, 100000, 8, 1, "f32"),
            ("C3-2e5", 1, 200000, 8, 1, "f32"), ("C3-1e5-f64", 1, 100000, 8, 1, "f64"),
+           ("T9-C2", 4, 5000, 9, 1, "f32"), ("T10-1e5", 1, 100000, 10, 1, "f32"),
            ("T12-1e5", 1, 100000, 12, 1, "f32"), ("T20-1e5", 1, 100000, 20, 1, "f32"),
            ("C4/8", 4, 20000, 12, 8, "f32"), ("C4/8-f64", 4, 20000, 12, 8, "f64"),
            ("C5", 8, 50000, 40, 1, "f32")]
