@@ -37,9 +37,18 @@ struct StepPlan {
   double nu0, nu1;            // mu_{t+1}
 };
 
-// Builds plan[t] for t < T (called by lanes t < T).  Returns a CCMPC_REC_* code or 0.
+// Builds plan[t] for t < T (called by lanes t < T).  Returns a CCMPC_REC_* code or 0.  On a
+// code every field of the plan is NaN: the plan lives in LDS, which keeps what the last
+// workgroup left there, and both kernels advance through a failed step like any other -- so a
+// failed cell's outputs are NaN from that step on, whatever ran before (ccmpc.h).
 __device__ int build_step(const double *__restrict__ mean, const double *__restrict__ cov,
                           int rows_src, int t, StepPlan &sp) {
+  auto fail = [&](int code) {
+    sp.a00 = sp.a01 = sp.a10 = sp.a11 = NAN;
+    sp.l00 = sp.l10 = sp.l11 = NAN;
+    sp.mu0 = sp.mu1 = sp.nu0 = sp.nu1 = NAN;
+    return code;
+  };
   auto blk = [&](int i, int j, double &a, double &b, double &c, double &d) {
     const double *p = cov + (2 * i) * rows_src + 2 * j;
     a = p[0];
@@ -52,7 +61,7 @@ __device__ int build_step(const double *__restrict__ mean, const double *__restr
   blk(t + 1, t + 1, n0, n1, n2, n3);  // cov_next
   blk(t + 1, t, c0, c1, c2, c3);      // C_t_tp1 = cross_cov[t+1][t]
   const double det = s0 * s3 - s1 * s2;
-  if (det == 0.0 || !isfinite(det)) return CCMPC_REC_SINGULAR;
+  if (det == 0.0 || !isfinite(det)) return fail(CCMPC_REC_SINGULAR);
   const double inv_det = 1.0 / det;
   const double i0 = s3 * inv_det, i1 = -s1 * inv_det, i2 = -s2 * inv_det, i3 = s0 * inv_det;
   sp.a00 = c0 * i0 + c1 * i2;
@@ -63,11 +72,11 @@ __device__ int build_step(const double *__restrict__ mean, const double *__restr
   const double k00 = n0 - (sp.a00 * c0 + sp.a01 * c1);
   const double k10 = n2 - (sp.a10 * c0 + sp.a11 * c1);
   const double k11 = n3 - (sp.a10 * c2 + sp.a11 * c3);
-  if (!(k00 > 0.0)) return CCMPC_REC_NOT_PD;
+  if (!(k00 > 0.0)) return fail(CCMPC_REC_NOT_PD);
   sp.l00 = sqrt(k00);
   sp.l10 = k10 / sp.l00;
   const double r = k11 - sp.l10 * sp.l10;
-  if (!(r > 0.0)) return CCMPC_REC_NOT_PD;
+  if (!(r > 0.0)) return fail(CCMPC_REC_NOT_PD);
   sp.l11 = sqrt(r);
   sp.mu0 = mean[2 * t];
   sp.mu1 = mean[2 * t + 1];
@@ -303,7 +312,18 @@ __global__ __launch_bounds__(ideal_threads(RB)) void ideal_gram_kernel(
   finalize_cell<Scheme16<RB>, NTH>(
       [&](int e) { return double2{stage_all[e], stage_all[e + 1]}; }, n, T, shift_s, S_lds, 0.0,
       0.0, mean, cov, mean_lds, nullptr);
-  if (MINK) minkowski_cell<NTH>(cov, mean_lds, T, cell, mp, lb_s, threadIdx.x);
+  if (MINK) {
+    minkowski_cell<NTH>(cov, mean_lds, T, cell, mp, lb_s, threadIdx.x);
+    // a failed cell: the pairs of the steps before the failure are built from finite moments and
+    // would read as good records; the reference raises for the whole cell, so every record of
+    // it carries the cell's code (status_s: every item of a cell builds the same plan)
+    if (status_s != 0) {
+      __syncthreads();  // the records are other threads' stores
+      ccmpc_halfspace *rec = mp.out_rec + static_cast<int64_t>(cell) * (T * (T - 1) / 2);
+      for (int p = threadIdx.x; p < T * (T - 1) / 2; p += NTH)
+        if (rec[p].status == 0) rec[p].status = status_s;
+    }
+  }
 }
 
 // samples per work item (multiple of 256 = 4 waves x 64): ~CCMPC_IDEAL_ITEMS items per launch

@@ -270,6 +270,19 @@ int ccmpc_affine_scale(const double *mean, const double *cov, int64_t T, int64_t
  *  up to a multiple of 4 (so the output is a valid ccmpc_moments store), dtype F64, slot t holds
  *  x_{t+1} (the reference's slot quirk).  T <= T_src - 1, ld >= n_cells * S.
  *  out_status[c]: 0 or CCMPC_REC_SINGULAR / CCMPC_REC_NOT_PD.
+ *
+ *  A failed cell (out_status[c] != 0; the reference raises LinAlgError for the frame, and the
+ *  host is expected to raise on the status) still has defined outputs, the same bits on every
+ *  run whatever ran on the device before:
+ *   - step t fails where det(Sigma_t) is 0 or not finite (SINGULAR; a NaN source covariance,
+ *     as the moments of a one-particle cell are, ends here) or Sigma_{t+1} - A_t C^T has no
+ *     Cholesky factor (NOT_PD); the status is the smallest code over the steps and the draw.
+ *   - slots before the first failed step hold the values a good cell would; from the first
+ *     failed step on every position, and with it every mean and covariance entry that touches
+ *     such a step, is NaN.  A failed x0 draw (x0 == NULL, cov_0 not PD) makes every slot NaN.
+ *   - in ccmpc_ideal_minkowski_cycle[_ex] every half-space record of the cell has a non-zero
+ *     status: its own code where it has one, the cell's code otherwise.
+ *  The other cells of the launch are not affected.
  * ------------------------------------------------------------------------------------- */
 int ccmpc_ideal_rollout(const double *prev_mean, const double *prev_cov, int64_t T_src,
                         const int32_t *src_cell, int64_t n_cells, int64_t T, int64_t n_samples,
