@@ -151,6 +151,7 @@ SIGNATURES = {
 }
 
 SELFTEST_MVOE, SELFTEST_TANGENT, SELFTEST_BOUND, SELFTEST_PAIR, SELFTEST_PRIM = 0, 1, 2, 3, 4
+SELFTEST_CHAIN = 5
 
 
 class CycleArgs(ctypes.Structure):

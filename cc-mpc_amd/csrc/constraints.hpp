@@ -1,9 +1,11 @@
 // Per-record math of the half-space generators, shared by the standalone kernels
 // (constraints.hip) and the fused moments -> half-space kernels (moments.hip, rollout.hip).
 //
-// Every step follows the reference's operation order (which matrix is formed first, the
-// strict '<' tie-break, the side test n.mean <= d) so that the integer outputs (which, side)
-// match bit-for-bit and the floating outputs match to rounding.
+// Every step that decides an integer output follows the reference's operation order (which
+// matrix is formed first, the strict '<' tie-break, the side test n.mean <= d) so that which and
+// side match bit-for-bit and the floating outputs match to rounding.  The MVOE fixed point is
+// the exception: it is set up and iterated in a shorter algebraic form (mvoe_chain), held to
+// the exact reference by tests/test_gpu_tail_precision.py and tests/test_gpu_tail_algebra.py.
 #pragma once
 #include "ccmpc_common.hpp"
 
@@ -84,8 +86,27 @@ __device__ __forceinline__ bool solve2(const M2 &s1, const M2 &s2, M2 &out) {
   return true;
 }
 
+// Build knob (profiles/r14): compute_mvoe's set-up from trace and determinant (0: by the LU
+// inverse, the product and its eigenvalues, as before r14).
+#ifndef CCMPC_MVOE_TRDET
+#define CCMPC_MVOE_TRDET 1
+#endif
+
+// Whether the LU with partial pivoting of m (inv2, as LAPACK's getrf) meets no zero pivot: the
+// `ok` flag of the tail's inverse and solve, by inv2's own instructions, for the forms that no
+// longer run the LU.  It decides the record's status and its NaNs, never a value of the chain.
+__device__ __forceinline__ bool lu_ok(const M2 &m) {
+  const bool piv = fabs(m.c) > fabs(m.a);
+  const double p0 = piv ? m.c : m.a, p1 = piv ? m.d : m.b;
+  const double q0 = piv ? m.a : m.c, q1 = piv ? m.b : m.d;
+  const double i11 = rcp_nr(p0);
+  const double l = q0 * i11;
+  const double u22 = q1 - l * p1;
+  return p0 != 0.0 && u22 != 0.0;
+}
+
 // One update of the MVOE fixed point, beta' = N rsqrt(N D) with N = 2 + s beta and
-// D = s + p2 beta (p2 = 2 l1 l2); see compute_mvoe.  Shared with CCMPC_SELFTEST_PRIM.
+// D = s + p2 beta (p2 = 2 l1 l2); see mvoe_chain.  Shared with CCMPC_SELFTEST_PRIM.
 __device__ __forceinline__ double mvoe_step(double s, double p2, double b) {
   const double N = fma(s, b, 2.0), D = fma(p2, b, s);
   const double x = N * D;
@@ -100,35 +121,80 @@ __device__ __forceinline__ double mvoe_step(double s, double p2, double b) {
   return fma(A * r, fma(0.375, r, 0.5), A);
 }
 
-// makeconstraint.py:7-38
-__device__ bool compute_mvoe(const M2 &S1, const M2 &S2, double tol, int maxiter, double &beta,
-                             M2 &Q) {
-  M2 M;
-  if (!solve2(S1, S2, M)) return false;
+// The serial part of compute_mvoe: the set-up (s, p2) and the fixed point's beta, with the `ok`
+// flag, which nothing here waits for.
+struct MvoeChain {
+  double s, p2, beta;
+  double prev;  // beta before the last update (CCMPC_SELFTEST_CHAIN; dead code elsewhere)
+  bool ok;
+};
+
+// Set-up.  With l1, l2 the eigenvalues of M = S1^-1 S2 the fixed point needs only s = l1 + l2 =
+// tr(M) and p2 = 2 l1 l2 = 2 det(M), and
+//   tr(S1^-1 S2) = tr(adj(S1) S2) / det S1,   det(M) = det S2 / det S1,
+// so one refined reciprocal of det S1 serves both: about 8 dependent f64 operations with one
+// transcendental.  (Until r14 the LU inverse of S1, the product M and M's eigenvalues through a
+// Goldschmidt square root stood here -- about 34 with three, twice per record -- and
+// l2 = tr / 2 - sqrt(disc) cancelled at high aspect; tests/test_tail_algebra_host.py holds both
+// forms against the exact reference.)  Plain products and differences: a compensated
+// determinant is deeper, and the accuracy tests do not ask for it.  `ok` is still the LU's
+// pivot test, so status is what it was on every input.
+//
+// Loop.  beta' = sqrt(sum 1/w / sum l/w), w = 1 + beta l  ==  sqrt(N / D) with N = w1 + w2 =
+// 2 + s beta and D = l1 w2 + l2 w1 = s + 2 p beta (p = l1 l2)  ==  N rsqrt(N D): the same fixed
+// point, each step one product, one hardware rsqrt and one second-order Goldschmidt step (7
+// dependent f64 operations, against 17 for an IEEE division + square root; the iteration is a
+// serial chain per record, so its latency is the tail's critical path).  One step is within a
+// few ulp of the exact sqrt(N / D): <= 2 ulp of rounding plus O(e^3)
+// (tests/test_gpu_tail_precision.py asserts <= 8 and gives the measured figure).  The stop test
+// is written "not |step| >= tol": the same boolean as "|step| < tol" on every ordered pair, and
+// a NaN update (a singular S1) leaves at once instead of running maxiter iterations that the LU
+// form's early return used to skip.
+__device__ __forceinline__ MvoeChain mvoe_chain(const M2 &S1, const M2 &S2, double tol,
+                                                int maxiter) {
+  MvoeChain c;
+#if CCMPC_MVOE_TRDET
+  c.ok = lu_ok(S1);
+  const double rdet = rcp_nr(S1.a * S1.d - S1.b * S1.c);
+  c.s = ((S1.d * S2.a - S1.b * S2.c) + (S1.a * S2.d - S1.c * S2.b)) * rdet;
+  c.p2 = 2.0 * ((S2.a * S2.d - S2.b * S2.c) * rdet);
+#else
+  M2 inv;
+  c.ok = inv2(S1, inv);
+  const M2 M = mul(inv, S2);
   const double half_tr = 0.5 * (M.a + M.d);
   const double hd = 0.5 * (M.a - M.d);
   const double disc = hd * hd + M.b * M.c;
   // complex pair (disc < 0): .real keeps the real part of both
   const double sd = disc >= 0.0 ? sqrt_gs(disc) : 0.0;
   const double l1 = half_tr + sd, l2 = half_tr - sd;
-  // beta' = sqrt(sum 1/w / sum l/w), w = 1 + beta l  ==  sqrt(N / D) with N = w1 + w2 =
-  // 2 + s beta and D = l1 w2 + l2 w1 = s + 2 p beta (s = l1 + l2, p = l1 l2)  ==  N rsqrt(N D):
-  // the same fixed point, each step one product, one hardware rsqrt and one second-order
-  // Goldschmidt step (7 dependent f64 operations, against 17 for an IEEE division + square
-  // root; the iteration is a serial chain per record, so its latency is the tail's critical
-  // path).  One step is within a few ulp of the exact sqrt(N / D): <= 2 ulp of rounding plus
-  // O(e^3) (tests/test_gpu_tail_precision.py asserts <= 8 and gives the measured figure).
-  const double s = l1 + l2, p2 = 2.0 * (l1 * l2);
-  double b = 1.0;
+  c.s = l1 + l2;
+  c.p2 = 2.0 * (l1 * l2);
+#endif
+  double b = 1.0, prev = 1.0;
   for (int it = 0; it < maxiter; ++it) {
-    const double bn = mvoe_step(s, p2, b);
-    const bool done = fabs(bn - b) < tol;
+    const double bn = mvoe_step(c.s, c.p2, b);
+    const bool done = !(fabs(bn - b) >= tol);
+    prev = b;
     b = bn;
     if (done) break;
   }
-  beta = b;
-  Q = add(scale(S1, 1.0 + rcp_nr(b)), scale(S2, 1.0 + b));
-  return true;
+  c.beta = b;
+  c.prev = prev;
+  return c;
+}
+
+// makeconstraint.py:7-38: beta by the fixed point, Q = S1 (1 + 1 / beta) + S2 (1 + beta).
+// Returns ok_in && the LU pivot test of S1; where that is false, beta and Q are NaN, by selects
+// on values the chain does not wait for (Q's through its S1 factor).
+__device__ bool compute_mvoe(const M2 &S1, const M2 &S2, double tol, int maxiter, double &beta,
+                             M2 &Q, bool ok_in = true) {
+  const MvoeChain c = mvoe_chain(S1, S2, tol, maxiter);
+  const bool ok = ok_in && c.ok;
+  const M2 S1n = {ok ? S1.a : NAN, ok ? S1.b : NAN, ok ? S1.c : NAN, ok ? S1.d : NAN};
+  beta = ok ? c.beta : NAN;
+  Q = add(scale(S1n, 1.0 + rcp_nr(c.beta)), scale(S2, 1.0 + c.beta));
+  return ok;
 }
 
 __device__ __forceinline__ double fro(const M2 &m) {
@@ -296,11 +362,12 @@ __device__ void minkowski_pair(const double *C, const double *mu, const double *
   // two MVOE calls (:915, :917-918)
   double b1 = NAN, b2 = NAN;
   M2 Q = {NAN, NAN, NAN, NAN}, QR = {NAN, NAN, NAN, NAN};
-  bool ok = pm.ok;
-  ok = ok && compute_mvoe(scale(pm.cov_infer, chi_r), scale(pm.cov_mu, chi_p), tol, maxiter, b1,
-                          Q);
+  // (a failed flag makes this call's and the next one's outputs NaN by selects; no branch sits
+  // between the chains)
+  bool ok = compute_mvoe(scale(pm.cov_infer, chi_r), scale(pm.cov_mu, chi_p), tol, maxiter, b1, Q,
+                         pm.ok);
   store_pair(&out->q01, Q.b, Q.d);
-  ok = ok && compute_mvoe(Q, M2{R * R, 0.0, 0.0, R * R}, tol, maxiter, b2, QR);
+  ok = compute_mvoe(Q, M2{R * R, 0.0, 0.0, R * R}, tol, maxiter, b2, QR, ok);
   if (!ok) status = CCMPC_REC_SINGULAR;
   store_pair(&out->r00, QR.a, QR.b);
   store_pair(&out->r11, QR.d, b1);

@@ -79,6 +79,17 @@ __global__ __launch_bounds__(64) void selftest_kernel(int kind, int64_t n,
       y[3] = mvoe_step(b, 1.0, a);  // one fixed-point update from beta = a with s = b, p2 = 1
       break;
     }
+    case CCMPC_SELFTEST_CHAIN: {  // compute_mvoe's set-up and loop, before Q is formed
+      const double *x = in + i * 8;
+      double *y = out + i * 5;
+      const MvoeChain c = mvoe_chain(ld_m2(x), ld_m2(x + 4), tol, maxiter);
+      y[0] = c.s;
+      y[1] = c.p2;
+      y[2] = c.beta;
+      y[3] = c.ok ? 1.0 : 0.0;
+      y[4] = c.prev;
+      break;
+    }
     default:
       break;
   }
@@ -115,7 +126,7 @@ extern "C" int ccmpc_poison_lds(double value, ccmpc_stream_t stream) {
 
 extern "C" int ccmpc_selftest(int kind, int64_t n, const double *in, double *out, double tol,
                               int32_t maxiter, ccmpc_stream_t stream) {
-  CCMPC_REQUIRE(kind >= CCMPC_SELFTEST_MVOE && kind <= CCMPC_SELFTEST_PRIM, "unknown kind");
+  CCMPC_REQUIRE(kind >= CCMPC_SELFTEST_MVOE && kind <= CCMPC_SELFTEST_CHAIN, "unknown kind");
   CCMPC_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "bad n");
   if (n == 0) return CCMPC_OK;
   CCMPC_REQUIRE(in && out, "null pointer");

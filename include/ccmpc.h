@@ -785,12 +785,16 @@ int ccmpc_risk_quantile(const void *positions, int dtype, int64_t ld, int64_t T,
  *  PRIM     in[n][2]  = a, b      out[n][4] = rcp_nr(b), div_nr(a, b), sqrt_gs(b), and one
  *           update of the MVOE fixed point from beta = a with s = b, p2 = 1
  *           (the hand-made reciprocal / division / square root of the MVOE chain)
+ *  CHAIN    in[n][8]  = S1, S2    out[n][5] = s = tr(S1^-1 S2), p2 = 2 det(S1^-1 S2), beta,
+ *           ok (1/0), beta before the last update
+ *           (compute_mvoe's set-up and fixed point before Q is formed; no NaN selects)
  * ------------------------------------------------------------------------------------- */
 #define CCMPC_SELFTEST_MVOE 0
 #define CCMPC_SELFTEST_TANGENT 1
 #define CCMPC_SELFTEST_BOUND 2
 #define CCMPC_SELFTEST_PAIR 3
 #define CCMPC_SELFTEST_PRIM 4
+#define CCMPC_SELFTEST_CHAIN 5
 int ccmpc_selftest(int kind, int64_t n, const double *in, double *out, double tol,
                    int32_t maxiter, ccmpc_stream_t stream);
 

@@ -15,10 +15,12 @@
 using namespace ccmpc;
 
 constexpr int T = 8, ROWS = 2 * T, P = T * (T - 1) / 2;
+constexpr int NTH = 256;  // the launch's workgroup size (minkowski_cell takes it at compile time)
 
 template <int PART>
-__global__ void part_kernel(const double *cov_g, const double *mean_g, MinkParams mp,
-                            unsigned long long *ticks, double *sink, int reps) {
+__global__ __launch_bounds__(NTH) void part_kernel(const double *cov_g, const double *mean_g,
+                                                   MinkParams mp, unsigned long long *ticks,
+                                                   double *sink, int reps) {
   __shared__ double cov[ROWS * ROWS];
   __shared__ double mean[ROWS];
   __shared__ double ref[ROWS + 3];
@@ -33,8 +35,8 @@ __global__ void part_kernel(const double *cov_g, const double *mean_g, MinkParam
   for (int r = 0; r < reps; ++r) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     if (PART == 5) {
-      minkowski_cell(cov, mean, T, 0, ref, ref[ROWS], ref[ROWS + 1], ref[ROWS + 2], mp, lb_s,
-                     threadIdx.x, blockDim.x);
+      minkowski_cell<NTH>(cov, mean, T, 0, ref, ref[ROWS], ref[ROWS + 1], ref[ROWS + 2], mp, lb_s,
+                          threadIdx.x);
     } else if (threadIdx.x < P) {
       int t, tau;
       pair_of(threadIdx.x, t, tau);
@@ -119,7 +121,7 @@ int main() {
   const char *names[] = {"pair_moments", "+ mvoe1", "+ mvoe2", "minkowski_pair",
                          "lower bound", "minkowski_cell", "pair -> LDS rec"};
   auto run = [&](auto kernel, int part) {
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(256), 0, 0, d_cov, d_mean, mp, d_ticks, d_sink, reps);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(NTH), 0, 0, d_cov, d_mean, mp, d_ticks, d_sink, reps);
     (void)hipDeviceSynchronize();
     std::vector<unsigned long long> ticks(reps);
     (void)hipMemcpy(ticks.data(), d_ticks, reps * 8, hipMemcpyDeviceToHost);
