@@ -344,9 +344,13 @@ __device__ __forceinline__ TangentFrame tangent_frame(double m0, double m1, doub
 
 // One (cell, t, tau) record except its lower bound, from the cell's 2T x 2T covariance C (row
 // stride `rows`) and mean mu (v8ideal/__init__.py:893-943), written straight to `out`.
-__device__ void minkowski_pair(const double *C, const double *mu, const double *ref, int rows,
+// TC: the compile-time horizon (0 = run-time; see minkowski_cell), which makes the row stride of
+// every covariance block an immediate.
+template <int TC = 0>
+__device__ void minkowski_pair(const double *C, const double *mu, const double *ref, int rows_arg,
                                int t, int tau, double chi_r, double chi_p, double R, double tol,
                                int maxiter, ccmpc_halfspace *out) {
+  const int rows = TC ? 2 * TC : rows_arg;
   // the tangent frame: computed ahead of the MVOE fixed points (straight-line code the
   // scheduler overlaps with the pair-moment chain; after the data-dependent loops it would be
   // pure latency)
@@ -400,11 +404,15 @@ __device__ void minkowski_pair(const double *C, const double *mu, const double *
 // and write their record field themselves.  Up to 128 pairs that lower-bound wave also takes
 // the per-t minimum (no workgroup barrier: callers must not rely on one after this call); past
 // that, the barrier needed before the per-t minimum is included.
-template <int NTH>
-__device__ void minkowski_cell(const double *C, const double *mu, int T, int cell,
+// TC, the compile-time horizon (0 = the run-time T): with it P and `half` are constants, so the
+// instance holds the one path its pair count takes (at T = 8 the 28 records on threads 0 .. 27,
+// the lower bounds on one wave of the other half) and not the generic pair loop beside it.
+template <int NTH, int TC = 0>
+__device__ void minkowski_cell(const double *C, const double *mu, int T_arg, int cell,
                                const double *ref, double chi_r, double chi_p, double gamma,
                                const MinkParams &mp, double *lb_s, int tid) {
   constexpr int nthreads = NTH;
+  const int T = TC ? TC : T_arg;
   const int rows = 2 * T;
   const int P = T * (T - 1) / 2;
   ccmpc_halfspace *rec = mp.out_rec + static_cast<int64_t>(cell) * P;
@@ -422,7 +430,8 @@ __device__ void minkowski_cell(const double *C, const double *mu, int T, int cel
       if (tid < P) {
         int t, tau;
         pair_of(tid, t, tau);
-        minkowski_pair(C, mu, ref, rows, t, tau, chi_r, chi_p, mp.R, mp.tol, mp.maxiter, rec + tid);
+        minkowski_pair<TC>(C, mu, ref, rows, t, tau, chi_r, chi_p, mp.R, mp.tol, mp.maxiter,
+                           rec + tid);
       }
       return;
     }
@@ -454,7 +463,7 @@ __device__ void minkowski_cell(const double *C, const double *mu, int T, int cel
       rec[p].lower_bound = lb;
     }
     if (!lb_side)
-      minkowski_pair(C, mu, ref, rows, t, tau, chi_r, chi_p, mp.R, mp.tol, mp.maxiter, rec + p);
+      minkowski_pair<TC>(C, mu, ref, rows, t, tau, chi_r, chi_p, mp.R, mp.tol, mp.maxiter, rec + p);
   }
   __syncthreads();
   for (int t = tid; t < T; t += nthreads) {

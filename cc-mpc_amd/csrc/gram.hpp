@@ -1006,10 +1006,11 @@ __host__ __device__ constexpr int gather_part_doubles(int E) {
 //    lanes l and l + 32 of one wave and meet by a cross-lane move, G0 + G1 in the lower lane:
 //    no LDS meeting point, one barrier less, the same bits.
 // The branch on root_n is workgroup-uniform.  Ends with a barrier.
-template <typename Sch, int NTH>
+template <typename Sch, int NTH, int TC = 0>
 __device__ __forceinline__ void gather_root(const double *__restrict__ root, int32_t root_n,
-                                            int rows, double *dst_lds, double *part_lds) {
+                                            int rows_arg, double *dst_lds, double *part_lds) {
   constexpr int E = Sch::E, GRAM = Sch::GRAM, H = Sch::GRAM / 2;
+  const int rows = TC ? 2 * TC : rows_arg;  // TC: the compile-time horizon (see finalize_cell)
   constexpr int HP = (H + 63) / 64 * 64;  // a group's slots, padded to whole waves
   constexpr bool kAllPairs = CCMPC_SPREAD_ALL_PAIRS && GRAM <= 256;  // T <= 10
   constexpr int nth = NTH;
@@ -1108,8 +1109,12 @@ __device__ __forceinline__ void gather_root(const double *__restrict__ root, int
 #ifndef CCMPC_ONE_ENTRY
 #define CCMPC_ONE_ENTRY 1
 #endif
-template <typename Sch, int NTH, typename Reader>
-__device__ void finalize_cell(Reader rd, int64_t cnt, int T, const double *shift_lds,
+//
+// TC, the compile-time horizon (0 = the run-time T; moments.hip's T = 8 instance passes 8): with
+// it `rows` is a constant here, so the entry decode's row tests and the covariance's addresses are
+// immediates on the last arriver's path instead of arithmetic on a loaded value.
+template <typename Sch, int NTH, int TC = 0, typename Reader>
+__device__ void finalize_cell(Reader rd, int64_t cnt, int T_arg, const double *shift_lds,
                               double *S_lds, double o0, double o1, double *__restrict__ mean,
                               double *__restrict__ cov, double *mean_lds, double *cov_lds,
                               const double *S_in = nullptr) {
@@ -1117,7 +1122,7 @@ __device__ void finalize_cell(Reader rd, int64_t cnt, int T, const double *shift
   constexpr int D = Sch::D;
   constexpr int nth = NTH;
   const int tid = threadIdx.x;
-  const int rows = 2 * T;
+  const int rows = TC ? 2 * TC : 2 * T_arg;
   const double n = static_cast<double>(cnt);
   // rd(e) returns the summed entry pair (e, e+1), e even.  S_in: the summed row sums already in
   // LDS (a slab there, entries GRAM.. after the caller's barrier) -- no copy, no barrier

@@ -268,14 +268,18 @@ struct EpilogueLds {
   int *flag;
 };
 
-template <typename Sch, int NTH, bool MINK, bool COV_IN_LDS, bool DEFER, typename Publish>
+// TC: the compile-time horizon (0 = the run-time T), handed on to every helper that takes T or
+// the row count.
+template <typename Sch, int NTH, bool MINK, bool COV_IN_LDS, bool DEFER, int TC = 0,
+          typename Publish>
 __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &loc, int32_t nit,
-                                              int T, const TreeLayout &tree,
+                                              int T_arg, const TreeLayout &tree,
                                               const double *__restrict__ origin,
                                               double *__restrict__ out_mean,
                                               double *__restrict__ out_cov, const MinkParams &mp,
                                               const EpilogueLds &L) {
   constexpr int E = Sch::E;
+  const int T = TC ? TC : T_arg;
   const int cell = loc.cell, rows = 2 * T;
   const double o0 = origin ? origin[2 * cell] : 0.0, o1 = origin ? origin[2 * cell + 1] : 0.0;
   double *mean = out_mean + static_cast<int64_t>(cell) * rows;
@@ -296,16 +300,16 @@ __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &lo
                                          &root, &root_n);
     PROBE_TS(4);
     if (!last) return;
-    gather_root<Sch, NTH>(root, root_n, rows, L.slab, L.cov);  // the exchange buffer is free here
+    gather_root<Sch, NTH, TC>(root, root_n, rows, L.slab, L.cov);  // the exchange buffer is free
     PROBE_GATHERED();
   }
-  finalize_cell<Sch, NTH>([&](int e) { return double2{L.slab[e], L.slab[e + 1]}; }, loc.cnt, T,
-                          L.shift, L.S, o0, o1, mean, cov, L.mean, COV_IN_LDS ? L.cov : nullptr,
-                          L.slab + Sch::GRAM);
+  finalize_cell<Sch, NTH, TC>([&](int e) { return double2{L.slab[e], L.slab[e + 1]}; }, loc.cnt,
+                              T, L.shift, L.S, o0, o1, mean, cov, L.mean,
+                              COV_IN_LDS ? L.cov : nullptr, L.slab + Sch::GRAM);
   PROBE_TS(5);
   if (MINK)
-    minkowski_cell<NTH>(COV_IN_LDS ? L.cov : cov, L.mean, T, cell, L.ref, L.ref[rows],
-                        L.ref[rows + 1], L.ref[rows + 2], mp, L.lb, threadIdx.x);
+    minkowski_cell<NTH, TC>(COV_IN_LDS ? L.cov : cov, L.mean, T, cell, L.ref, L.ref[rows],
+                            L.ref[rows + 1], L.ref[rows + 2], mp, L.lb, threadIdx.x);
   PROBE_TS(6);
 }
 
@@ -345,17 +349,29 @@ __device__ __forceinline__ double prefetch_tail(const MinkParams &mp, const Item
   return 0.0;
 }
 
-template <typename P, int RB, bool MINK, bool BAL>
+// TC, the compile-time horizon (the NTH pattern: 0 = the run-time T, 8 = T is 8, which launch()
+// picks for the plain launch at T = 8; CCMPC_T_CONST = 0 never picks it).  With T an argument the
+// RB = 1 instance knows neither rows = 16 nor P = 28: every loaded value carries a row mask, the
+// generic pair loop of minkowski_cell is compiled in beside the path T = 8 takes, and the
+// finaliser's decode and every covariance address are arithmetic on a loaded value.  T = 8 is
+// the horizon of the planning step and of every shrinking episode's first step.  TC stays the
+// LAST template parameter: the tools match this kernel by the prefix of its name.
+#ifndef CCMPC_T_CONST
+#define CCMPC_T_CONST 1
+#endif
+template <typename P, int RB, bool MINK, bool BAL, int TC = 0>
 // The fused half-space tail needs a few more registers than the 128 of 4 waves/SIMD at RB = 1.
 __global__ __launch_bounds__(Geo<RB>::THREADS,
                              (MINK && RB == 1) ? 3 : Geo<RB>::MIN_WAVES_PER_SIMD)
 void moments_kernel(
     const int64_t *__restrict__ cell_cnt, const int64_t *__restrict__ cell_off,
     const int32_t *__restrict__ cell_ref, int n_cells, const P *__restrict__ pos, int64_t ld,
-    int T, const double *__restrict__ origin, int lg_wq, TreeLayout tree,
+    int T_arg, const double *__restrict__ origin, int lg_wq, TreeLayout tree,
     double *__restrict__ out_mean, double *__restrict__ out_cov, MinkParams mp,
     int64_t whole) {
   using G = Geo<RB>;
+  static_assert(TC == 0 || 2 * TC == 16 * RB, "a constant horizon fills its row blocks exactly");
+  const int T = TC ? TC : T_arg;
   constexpr int NT = n_tiles(RB);
   constexpr int NACC = G::NACC;
   constexpr int D = 16 * RB;
@@ -460,7 +476,7 @@ void moments_kernel(
       if (w == 0 && g == 0) shift_lds[16 * bb + r] = sh[bb];
     }
     const EpilogueLds L{slab_lds, shift_lds, S_lds, mean_lds, xch, lb_s, ref_lds, &flag};
-    cell_epilogue<Scheme16<RB>, G::THREADS, MINK, COV_IN_LDS, DEFER>(
+    cell_epilogue<Scheme16<RB>, G::THREADS, MINK, COV_IN_LDS, DEFER, TC>(
         [&](double *dst, bool to_lds) {
           combine_waves<RB, NACC, G::NW>(acc, s1, xch, dst, to_lds);
         },
@@ -917,6 +933,15 @@ static int launch(const P *pos, int64_t ld, int T, const double *origin, const i
   }
   const int64_t items = max_items(n_cells, n_bound, int64_t(1) << store_lg_chunk(RB, n_bound));
   if (!tree_layout(ws, ws_bytes, items, n_cells, slab_doubles(RB), tree)) return CCMPC_ERR_WORKSPACE;
+  if constexpr (RB == 1 && CCMPC_T_CONST != 0) {
+    if (T == 8) {  // the instance that knows its horizon (moments_kernel, TC)
+      hipLaunchKernelGGL((moments_kernel<P, RB, MINK, false, 8>),
+                         dim3(static_cast<unsigned>(items)), dim3(threads), 0, s, cnt, off,
+                         MINK ? mp.cell_ref : nullptr, n_cells, pos, ld, T, origin, lg_wq, tree, mean,
+                         cov, mp, whole_cell_max(RB, n_bound));
+      return CCMPC_OK;
+    }
+  }
   hipLaunchKernelGGL((moments_kernel<P, RB, MINK, false>), dim3(static_cast<unsigned>(items)),
                      dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, n_cells, pos, ld, T,
                      origin, lg_wq, tree, mean, cov, mp, whole_cell_max(RB, n_bound));
