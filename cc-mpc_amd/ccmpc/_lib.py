@@ -50,6 +50,14 @@ AFFINE_DTYPE = np.dtype([
     ("which", "<i4"), ("side", "<i4"), ("status", "<i4"), ("t", "<i4"),
 ])
 assert HALFSPACE_DTYPE.itemsize == 128 and AFFINE_DTYPE.itemsize == 128
+# ccmpc_face_rec: one box face of one (cell, t); root / C hold r00 r01 r02 r11 r12 r22
+FACE_DTYPE = np.dtype([
+    ("mean", "<f8", (3,)), ("root", "<f8", (6,)), ("C", "<f8", (6,)),
+    ("status", "<i4"), ("t_face_chosen", "<u4"),
+])
+assert FACE_DTYPE.itemsize == 128
+FACE_NOMINAL, FACE_ROBUST = 0, 1   # CCMPC_FACE_*
+FACE_NO_CHOICE = 255               # CCMPC_FACE_NO_CHOICE
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -146,6 +154,10 @@ SIGNATURES = {
     "ccmpc_risk_quantile_workspace_bytes": (_SZ, [_I64, ctypes.c_int, _I64]),
     "ccmpc_risk_quantile": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64, _I64,
                                            _P, ctypes.c_int, _D, _P, _P, _SZ, _P, _P, _P, _P]),
+    "ccmpc_face_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "ccmpc_face_constraints": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64,
+                                              _I64, _P, _P, _P, _P, _P, ctypes.c_int, _D, _P,
+                                              _SZ, _P, _P]),
     "ccmpc_selftest": (ctypes.c_int, [ctypes.c_int, _I64, _P, _P, _D, _I32, _P]),
     "ccmpc_poison_lds": (ctypes.c_int, [_D, _P]),
 }

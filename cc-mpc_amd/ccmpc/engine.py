@@ -635,6 +635,60 @@ def affine_records(rec_bytes):
         rec_bytes.shape[:-1])
 
 
+FACE_KINDS = {"nominal": _lib.FACE_NOMINAL, "robust": _lib.FACE_ROBUST}
+
+
+def face_constraints(store, past_last, cell_gamma, kind="nominal", ref_traj=None, cell_ref=None,
+                     extent=(3.7, 1.79), car_r=4.47213, workspace=None, out_rec=None):
+    """Box-face chance-constraint records [C, T, 4] (raw bytes, see face_records) of a
+    ParticleStore: ccmpc_face_constraints (v8ideal/__init__.py:966-1376).  kind "nominal"
+    (root = sqrtm(C_f); with ref_traj [r, T, 2] it also marks the approx variant's face) or
+    "robust" (root = sqrt(|C_f|_F) I).  extent = (lon, lat), the reference's truck_d.
+    `workspace` must not be one the counter-bearing calls (moments, cycles, L4 split) share:
+    this call overwrites its head, which they need zero."""
+    lib = _lib.load()
+    if kind not in FACE_KINDS:
+        raise ValueError(f"kind must be one of {sorted(FACE_KINDS)}, got {kind!r}")
+    C, T, dev = store.n_cells, store.T, store.device
+    if out_rec is None:
+        out_rec = torch.empty((C, T, 4, 128), dtype=torch.uint8, device=dev)
+    # the small host inputs in one host-to-device copy: past_last [C, 2], gamma [C], extent [2]
+    host = np.concatenate([np.asarray(past_last, np.float64).reshape(C * 2),
+                           np.asarray(cell_gamma, np.float64).reshape(C),
+                           np.asarray(extent, np.float64).reshape(2)])
+    small = torch.as_tensor(host, device=dev)
+    pl, gm, ex = small[:2 * C], small[2 * C:3 * C], small[3 * C:]
+    if ref_traj is not None and not torch.is_tensor(ref_traj):
+        ref_traj = torch.as_tensor(np.asarray(ref_traj, np.float64).reshape(-1, T, 2), device=dev)
+    if cell_ref is not None and not torch.is_tensor(cell_ref):
+        cell_ref = torch.as_tensor(np.asarray(cell_ref, np.int32).reshape(C), device=dev)
+    need = lib.ccmpc_face_workspace_bytes(T, C, store.n_bound)
+    ws = (workspace or Workspace(dev)).get(need)
+    _lib.check(lib.ccmpc_face_constraints(
+        _p(store.pos), store.ccmpc_dtype, store.ld, T, _p(store.origin), _p(store.cell_off),
+        _p(store.cell_cnt), C, store.n_bound, _p(pl), _p(ex), _p(gm), _p(ref_traj), _p(cell_ref),
+        FACE_KINDS[kind], float(car_r), _p(ws), ws.numel(), _p(out_rec), _stream()),
+        "ccmpc_face_constraints")
+    out_rec._keepalive = (small, ref_traj, cell_ref, ws)
+    return out_rec
+
+
+def face_records(rec):
+    """Device (or host) face record bytes -> numpy structured array (FACE_DTYPE) of the same
+    leading shape, with the packed word split into t / face / chosen; synchronises."""
+    raw = rec.cpu().numpy() if torch.is_tensor(rec) else np.asarray(rec)
+    r = raw.reshape(-1).view(_lib.FACE_DTYPE).reshape(raw.shape[:-1])
+    out = np.empty(r.shape, dtype=np.dtype(_lib.FACE_DTYPE.descr[:-1] + [
+        ("t", "<i4"), ("face", "<i4"), ("chosen", "<i4")]))
+    for name in ("mean", "root", "C", "status"):
+        out[name] = r[name]
+    w = r["t_face_chosen"]
+    out["t"] = w >> 16
+    out["face"] = (w >> 8) & 0xff
+    out["chosen"] = w & 0xff
+    return out
+
+
 RiskAudit = collections.namedtuple("RiskAudit", "hit hit_any min_d2 rec_open open")
 RiskAudit.__doc__ = """risk_audit's device tensors: hit [C, T] int64, hit_any [C] int64, min_d2
 [C, T] float64 (None without a plan); rec_open [C, P] int64, open [C, T] int64 (None without

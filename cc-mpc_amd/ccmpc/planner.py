@@ -13,6 +13,9 @@ predict_ideal -- and runs every numeric step on the GPU through libccmpc.so:
       + ccmpc_l4 for vertices / A_union / b_union / yaw statistics
   compute_obstacle_constraints_GMM_affine                       v8ideal/__init__.py:1378-1539
   save_moments / predict_ideal                                  v8ideal/__init__.py:2575-2711
+  compute_obstacle_constraints_GMM / compute_robust_constraints_GMM /
+  compute_obstacle_constraints_GMM_approx (8-tuples)           v8ideal/__init__.py:966-1376
+      ccmpc_face_constraints: second-order-cone rows (SocConstraint, FaceConstraintList)
 
 Differences from the reference, all at the boundary:
   * constraints are HalfSpace records (cvxpy is not part of the compute path and is not
@@ -155,6 +158,136 @@ class HalfSpaceList:
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
+
+
+CAR_R = 4.47213   # v8ideal/__init__.py:978 ("this is actually a diameter")
+
+
+class SocConstraint:
+    """One box-face chance constraint of the "TCST" generators on xi = (x_t, y_t, 1):
+        mean . xi + gamma |root xi|_2 + offset <= M_big (1 - delta[face]) + S_big[face, t]
+    (v8ideal/__init__.py:1077-1082, :1210-1215; the approx rows :1353-1363 have no delta term).
+    root is sqrtm of the face coefficients' covariance (nominal, approx) or sqrt(|C|_F) I
+    (robust); offset = 0.5 CAR_R."""
+
+    __slots__ = ("ov", "k", "t", "face", "mean", "root", "gamma", "offset", "status")
+
+    def __init__(self, ov, k, t, face, mean, root, gamma, offset, status=0):
+        self.ov, self.k, self.t, self.face = ov, k, t, face
+        self.mean, self.root = mean, root
+        self.gamma, self.offset, self.status = gamma, offset, status
+
+    def value(self, xy):
+        """The left-hand side at the ego position xy."""
+        xi = np.array([float(xy[0]), float(xy[1]), 1.0])
+        return float(self.mean @ xi + self.gamma * np.linalg.norm(self.root @ xi) + self.offset)
+
+    def holds(self, xy, tol=0.0):
+        """The row with its face selected (delta = 1) and S_big = 0: value <= 0."""
+        return self.value(xy) <= tol
+
+    def expr(self, temp_x, delta=None, M_big=None, s_big=0.0):
+        """The reference's cvxpy row; delta = Delta2[(ov, k, t)] (None: the approx form)."""
+        import cvxpy as cp  # noqa: F401  (not installed in this image)
+        x = cp.hstack([temp_x[self.t][0], temp_x[self.t][1], 1.0])
+        lhs = self.mean @ x + self.gamma * cp.norm(self.root @ x, 2) + self.offset
+        rhs = s_big if delta is None else M_big * (1 - delta[self.face]) + s_big
+        return lhs <= rhs
+
+    def __repr__(self):
+        return (f"SocConstraint(ov={self.ov}, k={self.k}, t={self.t}, face={self.face}: "
+                f"[{self.mean[0]:.6g}, {self.mean[1]:.6g}, {self.mean[2]:.6g}] . xi + "
+                f"{self.gamma:.6g} |root xi| + {self.offset:.6g} <= ...)")
+
+
+class FaceDeltaSum:
+    """The `sum(delta_ijt) == 1` row that follows the four faces of (ov, k, t) in the nominal
+    and robust generators (:1083, :1216): at least one face must hold."""
+
+    __slots__ = ("ov", "k", "t")
+
+    def __init__(self, ov, k, t):
+        self.ov, self.k, self.t = ov, k, t
+
+    def expr(self, delta):
+        import cvxpy as cp  # noqa: F401
+        return cp.sum(delta) == 1
+
+    def __repr__(self):
+        return f"FaceDeltaSum(ov={self.ov}, k={self.k}, t={self.t})"
+
+
+FaceCheck = collections.namedtuple("FaceCheck", "ov k t values best holds")
+
+
+class FaceConstraintList:
+    """The `constraints` list of a box-face generator over one host copy of the face records
+    [C, T, 4], in the reference's append order: OV (gated ones only), mode, t; per (ov, k, t)
+    the four SocConstraint rows then a FaceDeltaSum (nominal, robust) or the one chosen row
+    (approx).  Objects are built when read.  A non-zero status inside a gated OV raises the
+    reference's exception up front."""
+
+    def __init__(self, rec, cell_of, gate, T, gamma, variant, offset):
+        self._rec, self._T, self._gamma = rec, int(T), np.asarray(gamma, float)
+        self.variant, self._offset = variant, float(offset)
+        self._cell_of = cell_of
+        self._cells = [c for c, (o, _) in enumerate(cell_of) if gate[o]]
+        for c in self._cells:
+            st = rec["status"][c, :self._T]
+            if st.any():
+                t, f = np.argwhere(st != 0)[0]
+                o, k = cell_of[c]
+                raise engine._lib.record_error(
+                    st[t, f], f"face constraint (ov={o}, k={k}, t={t}, face={f})")
+        self._per = 1 if variant == "approx" else 5
+
+    def __len__(self):
+        return len(self._cells) * self._T * self._per
+
+    def _row(self, c, t, f):
+        r = self._rec[c, t, f]
+        o, k = self._cell_of[c]
+        m = r["root"]
+        root = np.array([[m[0], m[1], m[2]], [m[1], m[3], m[4]], [m[2], m[4], m[5]]])
+        return SocConstraint(o, k, t, f, np.array(r["mean"]), root, float(self._gamma[c]),
+                             self._offset, int(r["status"]))
+
+    def chosen_face(self, c, t):
+        return int(np.argmax(self._rec["chosen"][c, t] == 1))
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        ct, f = divmod(i, self._per)
+        ci, t = divmod(ct, self._T)
+        c = self._cells[ci]
+        if self.variant == "approx":
+            return self._row(c, t, self.chosen_face(c, t))
+        if f == 4:
+            return FaceDeltaSum(*self._cell_of[c], t)
+        return self._row(c, t, f)
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def check(self, plan, tol=0.0):
+        """Is the plan (ego positions [T, >= 2]) feasible under these rows, with S_big = 0?
+        Per (ov, k, t): the four left-hand sides, the best face and whether the disjunction
+        (nominal, robust: some face <= 0) or the chosen row (approx) holds.  Returns
+        (list of FaceCheck, scene-level verdict)."""
+        plan = np.asarray(plan, float)
+        out = []
+        for c in self._cells:
+            o, k = self._cell_of[c]
+            for t in range(self._T):
+                v = np.array([self._row(c, t, f).value(plan[t]) for f in range(4)])
+                best = self.chosen_face(c, t) if self.variant == "approx" else int(np.argmin(v))
+                out.append(FaceCheck(o, k, t, v, best, bool(v[best] <= tol)))
+        return out, all(r.holds for r in out)
 
 
 class CellGrid:
@@ -982,6 +1115,66 @@ class MidlevelAgent:
         """v8ideal/__init__.py:1541-1878: the same generator without the covariance scale."""
         return self._affine_tangent_generator(params, ovehicles, eps_ura, Tsh, ref_traj,
                                               scaled=False)
+
+    def compute_obstacle_constraints_GMM(
+            self, params, ovehicles, Delta2, Omicron, temp_x, eps_ura, segments, Tsh):
+        """v8ideal/__init__.py:966-1094 ("nominal planning in the TCST paper"): per gated
+        (ov, k, t) four box-face second-order-cone rows and sum(delta) == 1.  Returns the
+        reference's 8-tuple (constraints, vertices, A_union, b_union, OVconstraint, direct,
+        ovStateMean_tau_1, ovStateCov_tau_1)."""
+        return self._face_generator(ovehicles, eps_ura, Tsh, "nominal")
+
+    def compute_robust_constraints_GMM(
+            self, params, ovehicles, Delta2, Omicron, temp_x, eps_ura, segments, Tsh):
+        """v8ideal/__init__.py:1096-1229 ("robust planning in the TCST paper"): the same rows
+        with sqrt(|C|_F) |xi| in place of |sqrtm(C) xi|."""
+        return self._face_generator(ovehicles, eps_ura, Tsh, "robust")
+
+    def compute_obstacle_constraints_GMM_approx(
+            self, params, ovehicles, Delta2, Omicron, temp_x, eps_ura, segments, Tsh, ref_traj):
+        """v8ideal/__init__.py:1231-1376: of the four nominal rows only the one with the
+        smallest left-hand side at the reference trajectory, without a delta."""
+        return self._face_generator(ovehicles, eps_ura, Tsh, "approx", ref_traj)
+
+    def _face_workspace(self):
+        """A workspace of its own: ccmpc_face_constraints keeps no counters and overwrites the
+        head of its workspace, which the one-launch reductions sharing self._ws need zero."""
+        ws = getattr(self, "_ws_faces", None)
+        if ws is None:
+            ws = self._ws_faces = engine.Workspace(self.device)
+        return ws
+
+    def _face_generator(self, ovehicles, eps_ura, Tsh, variant, ref_traj=None):
+        """The three box-face generators: one ccmpc_face_constraints call on the scene's store.
+        The rows are second-order cones, not half-spaces: _last_rec and the audit / calibration
+        sources stay unset, so solve_planning_qp, audit_plan and calibrate_constraints refuse
+        them as they refuse any step without half-space records."""
+        T = int(Tsh)
+        scene = self._scene(ovehicles)
+        K = scene.K
+        if T > scene.T:
+            raise ValueError("the box-face generators run on the prediction horizon's particles")
+        gamma = self._cell_risk_host(np.asarray(eps_ura), K)[:, 2]
+        ref = self._ref(ref_traj, scene.T) if variant == "approx" else None
+        mean, cov = engine.moments(scene.store, workspace=self._ws)
+        rec = engine.face_constraints(
+            scene.store, scene.cell_past_last(), gamma,
+            kind="robust" if variant == "robust" else "nominal", ref_traj=ref,
+            car_r=CAR_R, workspace=self._face_workspace())
+        h = engine.face_records(rec)
+        self.last_records = h
+        self._last_rec = None
+        self._audit_src = None
+        mean0 = mean[:, 0, :].cpu().numpy()
+        cov0 = cov[:, 0:2, 0:2].cpu().numpy()
+        last = mean0[_last_cells(tuple(K))].tolist()             # last mode wins (:1008-1019)
+        gate = [not (x >= 190 or y <= -80) for x, y in last]
+        cons = FaceConstraintList(h, scene.cell_of, gate, T, gamma, variant,
+                                  0.5 * CAR_R)
+        st_mean, st_cov = self._state_stats(scene, mean0, cov0)
+        vertices, A_union, b_union = self._l4_lists(scene)
+        return (cons, vertices, A_union, b_union, any(gate), _object_grid(scene.O), st_mean,
+                st_cov)
 
     def _affine_tangent_generator(self, params, ovehicles, eps_ura, Tsh, ref_traj, scaled):
         T, ph = int(Tsh), self.prediction_horizon

@@ -3,6 +3,7 @@
 
 #include "audit.hpp"
 #include "ccmpc_common.hpp"
+#include "faces.hpp"
 #include "quantile.hpp"
 
 namespace ccmpc {
@@ -270,6 +271,65 @@ extern "C" int ccmpc_risk_audit(const void *positions, int dtype, int64_t ld, in
                            static_cast<const unsigned char *>(rec), rec_kind, P, R * R,
                            out_hit, out_hit_any, out_min_d2, out_rec_open, out_open};
   const int rc = ccmpc::launch_risk_audit(a, ccmpc::as_stream(stream));
+  CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
+  CCMPC_LAUNCH_CHECK();
+  return CCMPC_OK;
+}
+
+// ---- Box-face chance constraints (faces.hip) ------------------------------------------------
+extern "C" size_t ccmpc_face_workspace_bytes(int64_t T, int64_t n_cells,
+                                             int64_t n_particles_bound) {
+  if (T < 1 || T > ccmpc::kFaceMaxT || n_cells < 0 || n_cells >= (1 << 30) ||
+      n_particles_bound < 0)
+    return 0;
+  return ccmpc::face_workspace_bytes(T, n_cells, n_particles_bound);
+}
+
+extern "C" int ccmpc_face_constraints(const void *positions, int dtype, int64_t ld, int64_t T,
+                                      const double *origin, const int64_t *cell_off,
+                                      const int64_t *cell_cnt, int64_t n_cells,
+                                      int64_t n_particles_bound, const double *past_last,
+                                      const double *extent, const double *cell_gamma,
+                                      const double *ref_traj, const int32_t *cell_ref, int kind,
+                                      double car_r, void *workspace, size_t workspace_bytes,
+                                      ccmpc_face_rec *out_rec, ccmpc_stream_t stream) {
+  static_assert(sizeof(ccmpc_face_rec) == 128, "ccmpc_face_rec is 128 bytes");
+  CCMPC_REQUIRE(T >= 1 && T <= ccmpc::kFaceMaxT, "T must be in [1, 40]");
+  CCMPC_REQUIRE(kind == CCMPC_FACE_NOMINAL || kind == CCMPC_FACE_ROBUST, "unknown kind");
+  CCMPC_REQUIRE(std::isfinite(car_r), "car_r must be finite");
+  CCMPC_REQUIRE(n_cells >= 0 && n_cells < (1 << 30), "bad n_cells");
+  CCMPC_REQUIRE(n_particles_bound >= 0, "bad n_particles_bound");
+  CCMPC_REQUIRE(dtype == CCMPC_F64 || dtype == CCMPC_F32, "bad dtype");
+  CCMPC_REQUIRE(ld % 4 == 0 && ld > 0, "ld must be a positive multiple of 4");
+  if (n_cells == 0) return CCMPC_OK;
+  CCMPC_REQUIRE(positions && cell_off && cell_cnt && past_last && extent && cell_gamma && out_rec,
+                "null pointer");
+  CCMPC_REQUIRE(ccmpc::aligned(positions, 16), "positions must be 16-byte aligned");
+  CCMPC_REQUIRE(ccmpc::aligned(out_rec, 8), "out_rec must be 8-byte aligned");
+  CCMPC_REQUIRE(workspace && ccmpc::aligned(workspace, 256), "workspace must be 256-byte aligned");
+  if (workspace_bytes < ccmpc::face_workspace_bytes(T, n_cells, n_particles_bound)) {
+    ccmpc::set_error("ccmpc_face_constraints: workspace too small");
+    return CCMPC_ERR_WORKSPACE;
+  }
+  ccmpc::FaceArgs a{};
+  a.pos = positions;
+  a.dtype = dtype;
+  a.ld = ld;
+  a.T = static_cast<int>(T);
+  a.origin = origin;
+  a.off = cell_off;
+  a.cnt = cell_cnt;
+  a.n_cells = static_cast<int>(n_cells);
+  a.past_last = past_last;
+  a.extent = extent;
+  a.gamma = cell_gamma;
+  a.ref = ref_traj;
+  a.cell_ref = cell_ref;
+  a.kind = kind;
+  a.car_r = car_r;
+  a.rec = out_rec;
+  const int rc = ccmpc::launch_face_constraints(a, n_particles_bound, workspace,
+                                                ccmpc::as_stream(stream));
   CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
   CCMPC_LAUNCH_CHECK();
   return CCMPC_OK;

@@ -769,6 +769,67 @@ int ccmpc_risk_quantile(const void *positions, int dtype, int64_t ld, int64_t T,
                         int32_t *out_status, ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Box-face chance constraints (the "TCST" family): the second-order-cone row data of
+ * compute_obstacle_constraints_GMM (v8ideal/__init__.py:966-1094, "nominal"),
+ * compute_robust_constraints_GMM (:1096-1229, "robust") and
+ * compute_obstacle_constraints_GMM_approx (:1231-1376, nominal rows with ref_traj given), for
+ * every (cell, t) in one call.  Replaces the per-(cell, t) loop that stacks the four 3 x N face
+ * coefficient arrays (:1058-1061), takes np.mean / np.cov of each and sqrtm (nominal, approx)
+ * or sqrt(|C|_F) (robust) of the covariance.
+ *
+ * Per particle at step t: (x, y) its world position, (c, s) the unit vector of its step delta
+ * (ovehicle.py:72-76: p_t - p_{t-1}, step 0 from past_last; formed exactly as ccmpc_l4 forms
+ * it, a zero step giving c = 1, s = 0), lon = extent[0], lat = extent[1]:
+ *   a1 = (-c,  s,   c x - s y + lat/2)      a3 = ( c, -s,  -c x + s y + lat/2)
+ *   a2 = (-s, -c,   s x + c y + lon/2)      a4 = ( s,  c,  -s x - c y + lon/2)
+ * Face f (0..3 for a1..a4) of (cell, t):  mean_f . xi + Gamma |root_f xi|_2 + 0.5 car_r <= ...
+ * with xi = (X, Y, 1), mean_f = the particle mean of a_f, C_f its covariance (ddof = 1),
+ * root_f = sqrtm(C_f) (CCMPC_FACE_NOMINAL) or sqrt(|C_f|_F) I (CCMPC_FACE_ROBUST), Gamma =
+ * cell_gamma[c].  Faces 2 and 3 are the mirror images of 0 and 1 (a3 = -a1 + (0, 0, lat)), so
+ * they share C and root with them; only two moment sets are reduced from the particles.
+ * The sums run over coefficients shifted by the cell's first particle (its position and its
+ * coefficient vector), in float64, chunk partials added in chunk order: bit-reproducible.
+ *
+ * One record per (cell, t, face), 128 bytes. */
+typedef struct ccmpc_face_rec {
+  double mean[3];         /* np.mean(a_f, axis=1)                       (:1067-1070)           */
+  double root[6];         /* r00 r01 r02 r11 r12 r22 of the symmetric root_f (:1072-1075);
+                             robust: s = sqrt(|C_f|_F) on the diagonal, 0 elsewhere (:1205-1208) */
+  double C[6];            /* c00 c01 c02 c11 c12 c22 of np.cov(a_f)                             */
+  int32_t status;         /* 0, CCMPC_REC_NONFINITE (fewer than 2 particles, or a non-finite
+                             moment) or CCMPC_REC_NOT_PSD (an eigenvalue below -64 eps lambda_max;
+                             nominal only).  A failed record's numeric fields are all NaN.      */
+  uint32_t t_face_chosen; /* (t << 16) | (face << 8) | chosen; chosen = 1 for the face with the
+                             smallest left-hand side at xi_ref = (ref_traj[r][t], 1), first index
+                             on equality (val.index(min(val)), :1352), 0 for the other three, and
+                             CCMPC_FACE_NO_CHOICE where ref_traj is NULL or a face of (c, t) failed */
+} ccmpc_face_rec;
+#define CCMPC_FACE_NOMINAL 0
+#define CCMPC_FACE_ROBUST 1
+#define CCMPC_FACE_NO_CHOICE 255u
+/*  past_last[c][2]   world-frame past[-1] of the cell's OV, as ccmpc_l4
+ *  extent            device, {lon, lat}: the reference hard-codes truck_d = (3.7, 1.79) (:976-977)
+ *  cell_gamma[c]     norm.ppf(1 - eps_ura[ov, k] / Tpred) (:1064-1065, :1196-1197, :1330-1331)
+ *  ref_traj[r][T][2] nullable; cell c uses row cell_ref[c] (NULL -> 0) (approx, :1343-1352)
+ *  car_r             CAR_R = 4.47213 (:978); the rows add 0.5 car_r
+ *  out_rec[c][T][4]  written in full by every call: the caller initialises nothing
+ * Workspace: ccmpc_face_workspace_bytes (0 for T > 40 or bad arguments), 256-byte aligned, NOT
+ * initialised by the caller and holding no counters: two launches, no atomics (the first writes
+ * one partial per (cell, t, chunk of 2048 particles), the second, one wave per
+ * (cell, t), adds them in chunk order, undoes the shift, and takes the principal root by a
+ * cyclic Jacobi eigen-decomposition of 8 sweeps).  The call overwrites the head of its workspace:
+ * do not hand it one whose arrival counters another call needs zero (the workspace contract of
+ * ccmpc_moments).  cell_off / ld multiples of 4, as ccmpc_moments;
+ * n_particles_bound >= sum(cell_cnt) sizes the grid. */
+size_t ccmpc_face_workspace_bytes(int64_t T, int64_t n_cells, int64_t n_particles_bound);
+int ccmpc_face_constraints(const void *positions, int dtype, int64_t ld, int64_t T,
+                           const double *origin, const int64_t *cell_off, const int64_t *cell_cnt,
+                           int64_t n_cells, int64_t n_particles_bound, const double *past_last,
+                           const double *extent, const double *cell_gamma, const double *ref_traj,
+                           const int32_t *cell_ref, int kind, double car_r, void *workspace,
+                           size_t workspace_bytes, ccmpc_face_rec *out_rec, ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * TEST ONLY (not a reference interface): the half-space tail's device functions -- the ones
  * ccmpc_minkowski_cycle / ccmpc_minkowski / ccmpc_affine_scale run per record -- on n batched
  * inputs, so the reference's component golden vectors reach the device arithmetic.  Device
