@@ -359,19 +359,26 @@ __device__ __forceinline__ double prefetch_tail(const MinkParams &mp, const Item
 #ifndef CCMPC_T_CONST
 #define CCMPC_T_CONST 1
 #endif
+//
+// Argument order: the first 14 dwords (56 bytes) are everything locate and the particle addresses
+// need -- the three tables, pos, ld, n_cells, lg_wq, whole, T -- because the build asks for them to
+// be in SGPRs when a wave starts (kernel-argument preload, CCMPC_KERNARG_PRELOAD in the Makefile:
+// 16 user SGPRs less the two of the argument pointer).  An argument past byte 56 is a scalar
+// load, and a use of one ahead of locate puts a wait for a cold line in front of the table
+// loads: keep origin, tree, the outputs and mp behind the stream.
 template <typename P, int RB, bool MINK, bool BAL, int TC = 0>
 // The fused half-space tail needs a few more registers than the 128 of 4 waves/SIMD at RB = 1.
 __global__ __launch_bounds__(Geo<RB>::THREADS,
                              (MINK && RB == 1) ? 3 : Geo<RB>::MIN_WAVES_PER_SIMD)
 void moments_kernel(
     const int64_t *__restrict__ cell_cnt, const int64_t *__restrict__ cell_off,
-    const int32_t *__restrict__ cell_ref, int n_cells, const P *__restrict__ pos, int64_t ld,
-    int T_arg, const double *__restrict__ origin, int lg_wq, TreeLayout tree,
-    double *__restrict__ out_mean, double *__restrict__ out_cov, MinkParams mp,
-    int64_t whole) {
+    const int32_t *__restrict__ cell_ref, const P *__restrict__ pos, int64_t ld, int n_cells,
+    int lg_wq, int32_t whole32, int T_arg, const double *__restrict__ origin, TreeLayout tree,
+    double *__restrict__ out_mean, double *__restrict__ out_cov, MinkParams mp) {
   using G = Geo<RB>;
   static_assert(TC == 0 || 2 * TC == 16 * RB, "a constant horizon fills its row blocks exactly");
   const int T = TC ? TC : T_arg;
+  const int64_t whole = whole32;  // <= CCMPC_WHOLE_CELL_MAX: one dword of the preloaded 14
   constexpr int NT = n_tiles(RB);
   constexpr int NACC = G::NACC;
   constexpr int D = 16 * RB;
@@ -654,9 +661,10 @@ constexpr int m4_occ(int nb) {
 template <typename P, int NB, bool MINK, bool BAL>
 __global__ __launch_bounds__(kThreads4, m4_occ<P>(NB)) void moments4_kernel(
     const int64_t *__restrict__ cell_cnt, const int64_t *__restrict__ cell_off,
-    const int32_t *__restrict__ cell_ref, int n_cells, const P *__restrict__ pos, int64_t ld,
-    int T, const double *__restrict__ origin, int lg_wq, TreeLayout tree,
+    const int32_t *__restrict__ cell_ref, const P *__restrict__ pos, int64_t ld, int n_cells,
+    int lg_wq, int T, const double *__restrict__ origin, TreeLayout tree,
     double *__restrict__ out_mean, double *__restrict__ out_cov, MinkParams mp) {
+  // moments_kernel's argument order (it has no `whole`): the first 13 dwords are preloaded
   using Sch = Scheme4<NB>;
   constexpr int NP = Sch::NP, D = Sch::D, E = Sch::E;
   __shared__ double xch[kNW4 * Combine4Layout<NB>::XS];
@@ -905,7 +913,9 @@ __global__ __launch_bounds__(RootGeo<RB>::THREADS) void root_finalize_kernel(
 #ifndef CCMPC_WHOLE_CELL_MAX
 #define CCMPC_WHOLE_CELL_MAX 1024
 #endif
-inline int64_t whole_cell_max(int rb, int64_t n_bound) {
+static_assert(CCMPC_WHOLE_CELL_MAX >= 0 && CCMPC_WHOLE_CELL_MAX <= INT32_MAX,
+              "the kernel takes the cap as an int32 argument");
+inline int32_t whole_cell_max(int rb, int64_t n_bound) {
   return (rb == 1 && n_bound <= (int64_t(1) << CCMPC_LG_TINY_INPUT)) ? CCMPC_WHOLE_CELL_MAX : 0;
 }
 
@@ -923,8 +933,8 @@ static int launch(const P *pos, int64_t ld, int T, const double *origin, const i
                      tree))
       return CCMPC_ERR_WORKSPACE;
     hipLaunchKernelGGL((moments_kernel<P, RB, MINK, true>), dim3(static_cast<unsigned>(grid)),
-                       dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, n_cells, pos, ld,
-                       T, origin, lg_wq, tree, mean, cov, mp, int64_t(0));
+                       dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, pos, ld, n_cells,
+                       lg_wq, int32_t(0), T, origin, tree, mean, cov, mp);
     if (defer_root(RB, MINK, true))
       hipLaunchKernelGGL((root_finalize_kernel<P, RB>),
                          dim3(static_cast<unsigned>(n_cells * n_tiles(RB))), dim3(RootGeo<RB>::THREADS), 0,
@@ -937,14 +947,14 @@ static int launch(const P *pos, int64_t ld, int T, const double *origin, const i
     if (T == 8) {  // the instance that knows its horizon (moments_kernel, TC)
       hipLaunchKernelGGL((moments_kernel<P, RB, MINK, false, 8>),
                          dim3(static_cast<unsigned>(items)), dim3(threads), 0, s, cnt, off,
-                         MINK ? mp.cell_ref : nullptr, n_cells, pos, ld, T, origin, lg_wq, tree, mean,
-                         cov, mp, whole_cell_max(RB, n_bound));
+                         MINK ? mp.cell_ref : nullptr, pos, ld, n_cells, lg_wq,
+                         whole_cell_max(RB, n_bound), T, origin, tree, mean, cov, mp);
       return CCMPC_OK;
     }
   }
   hipLaunchKernelGGL((moments_kernel<P, RB, MINK, false>), dim3(static_cast<unsigned>(items)),
-                     dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, n_cells, pos, ld, T,
-                     origin, lg_wq, tree, mean, cov, mp, whole_cell_max(RB, n_bound));
+                     dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, pos, ld, n_cells,
+                     lg_wq, whole_cell_max(RB, n_bound), T, origin, tree, mean, cov, mp);
   return CCMPC_OK;
 }
 
@@ -962,15 +972,15 @@ static int launch4(const P *pos, int64_t ld, int T, const double *origin, const 
                      tree))
       return CCMPC_ERR_WORKSPACE;
     hipLaunchKernelGGL((moments4_kernel<P, NB, MINK, true>), dim3(static_cast<unsigned>(grid)),
-                       dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, n_cells, pos, ld,
-                       T, origin, lg_wq, tree, mean, cov, mp);
+                       dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, pos, ld, n_cells,
+                       lg_wq, T, origin, tree, mean, cov, mp);
     return CCMPC_OK;
   }
   const int64_t items = max_items(n_cells, n_bound, int64_t(1) << (lg_wq + 2));
   if (!tree_layout(ws, ws_bytes, items, n_cells, Scheme4<NB>::E, tree)) return CCMPC_ERR_WORKSPACE;
   hipLaunchKernelGGL((moments4_kernel<P, NB, MINK, false>), dim3(static_cast<unsigned>(items)),
-                     dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, n_cells, pos, ld, T,
-                     origin, lg_wq, tree, mean, cov, mp);
+                     dim3(threads), 0, s, cnt, off, MINK ? mp.cell_ref : nullptr, pos, ld, n_cells,
+                     lg_wq, T, origin, tree, mean, cov, mp);
   return CCMPC_OK;
 }
 
