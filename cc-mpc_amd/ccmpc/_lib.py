@@ -58,6 +58,9 @@ FACE_DTYPE = np.dtype([
 assert FACE_DTYPE.itemsize == 128
 FACE_NOMINAL, FACE_ROBUST = 0, 1   # CCMPC_FACE_*
 FACE_NO_CHOICE = 255               # CCMPC_FACE_NO_CHOICE
+# ccmpc_face_cuts: out_state (CCMPC_SOCP_*) and the status of an empty pool record
+SOCP_OK, SOCP_CUT, SOCP_BAD_ROW, SOCP_BAD_LAYOUT = range(4)
+CUT_EMPTY = 1
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -158,6 +161,8 @@ SIGNATURES = {
     "ccmpc_face_constraints": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64,
                                               _I64, _P, _P, _P, _P, _P, ctypes.c_int, _D, _P,
                                               _SZ, _P, _P]),
+    "ccmpc_face_cuts": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _P, _D, _P, _I64, _I32, _I32, _D,
+                                       _I32, _P, _P, _P, _P, _P, _P]),
     "ccmpc_selftest": (ctypes.c_int, [ctypes.c_int, _I64, _P, _P, _D, _I32, _P]),
     "ccmpc_poison_lds": (ctypes.c_int, [_D, _P]),
 }

@@ -689,6 +689,49 @@ def face_records(rec):
     return out
 
 
+def face_cuts(rec, T, scene_cell, n_cells, cell_gamma, plan, pool, pool_cell, out_g, out_viol,
+              out_state, round, max_rounds, tol_g=1e-6, face_sel=None, car_r=4.47213,
+              only_violated=False):
+    """One round of outer-approximation cuts of the face rows (ccmpc_face_cuts): every selected
+    (cell, t) row of `rec` [n_cells, T, 4, 128] linearised at `plan` [S, T, ld >= 2] (the QP's
+    X [S, T, 4] is read in place) into region `round` of `pool` [(max_rounds + 1) n_cells, T, 32],
+    which PlanningQP reads with kind REC_AFFINE_COMPACT and scene_cell = pool_cell.  scene_cell /
+    pool_cell: int64 [S + 1] device tensors; face_sel: int32 [n_cells, T] or None (the records'
+    own choice); out_g [n_cells, T], out_viol [S] float64 and out_state [S] int32 are written in
+    full.  Every tensor is a contiguous device tensor; the sizes are checked here because the
+    kernel reads raw pointers.  Enqueues one launch on the current stream, never synchronises."""
+    lib = _lib.load()
+    T, C, S = int(T), int(n_cells), int(scene_cell.numel()) - 1
+    regions = int(max_rounds) + 1
+
+    def need(t, name, dtype, numel):
+        if (not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != dtype
+                or not t.is_contiguous() or t.numel() < numel):
+            raise ValueError(f"{name}: contiguous {dtype} device tensor of >= {numel} elements "
+                             "required")
+    if S < 0 or pool_cell.numel() != S + 1:
+        raise ValueError("scene_cell and pool_cell must both hold S + 1 offsets")
+    if plan.dim() != 3 or plan.shape[0] != S or plan.shape[1] != T or plan.shape[2] < 2:
+        raise ValueError(f"plan must be [{S}, {T}, >= 2]")
+    need(rec, "rec", torch.uint8, C * T * 4 * 128)
+    need(scene_cell, "scene_cell", torch.int64, S + 1)
+    need(pool_cell, "pool_cell", torch.int64, S + 1)
+    need(cell_gamma, "cell_gamma", torch.float64, C)
+    need(plan, "plan", torch.float64, 0)
+    need(pool, "pool", torch.uint8, regions * C * T * 32)
+    need(out_g, "out_g", torch.float64, C * T)
+    need(out_viol, "out_viol", torch.float64, S)
+    need(out_state, "out_state", torch.int32, S)
+    if face_sel is not None:
+        need(face_sel, "face_sel", torch.int32, C * T)
+    _lib.check(lib.ccmpc_face_cuts(
+        _p(rec), T, S, _p(scene_cell), _p(face_sel), _p(cell_gamma), float(car_r), _p(plan),
+        int(plan.shape[2]), int(round), int(max_rounds), float(tol_g), int(bool(only_violated)),
+        _p(pool), _p(pool_cell), _p(out_g), _p(out_viol), _p(out_state), _stream()),
+        "ccmpc_face_cuts")
+    return out_g, out_viol, out_state
+
+
 RiskAudit = collections.namedtuple("RiskAudit", "hit hit_any min_d2 rec_open open")
 RiskAudit.__doc__ = """risk_audit's device tensors: hit [C, T] int64, hit_any [C] int64, min_d2
 [C, T] float64 (None without a plan); rec_open [C, P] int64, open [C, T] int64 (None without

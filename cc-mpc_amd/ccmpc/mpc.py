@@ -12,6 +12,7 @@ solved on the device, batched over scenes, straight from the generators' records
 Every tensor is a torch device tensor; nothing here synchronises except the explicit
 ``.cpu()`` of results by the caller.  There is no CPU fallback.
 """
+import collections
 import ctypes
 import math
 import os
@@ -169,6 +170,109 @@ class PlanningQP:
         if self.u_order == U_ORDER_F:
             return u.reshape(-1, 2, self.T).transpose(1, 2)
         return u.reshape(-1, self.T, 2)
+
+
+SOCP_OK = 0            # max g <= tol_g at the returned plan
+SOCP_INFEASIBLE = 1    # some round's QP returned QP_MAXITER: the cone programme is infeasible
+SOCP_NUMERIC = 2       # QP_NUMERIC, passed through
+SOCP_MAXROUNDS = 8     # max_rounds QPs solved, max g still above tol_g
+SOCP_BAD_ROW = 16      # a selected face record failed, or has no chosen face
+
+SocpResult = collections.namedtuple("SocpResult", "u X cost status rounds viol costs")
+SocpResult.__doc__ = """PlanningSOCP.solve's answer: u [S, 2T], X [S, T, 4], cost [S] device
+tensors (each scene's values of the round that ended it); status [S] (SOCP_*), rounds [S] (QPs
+solved) and viol [S] (max g at X) NumPy arrays; costs [rounds, S] the QP cost of every round
+(NaN after a scene ended)."""
+
+
+class PlanningSOCP:
+    """The plan under the box-face cone rows, batched over S scenes: outer approximation
+    (Kelley's cutting planes) over PlanningQP.  Round 0 cuts every selected row at the caller's
+    linearisation point; every later round is one QP over all cuts so far (PlanningQP on the
+    pool, kind REC_AFFINE_COMPACT), one ccmpc_face_cuts launch at its X, and one small
+    read-back (state, violation, QP status and cost of every scene).  A scene ends when max g
+    <= tol_g (SOCP_OK), when its QP is infeasible (SOCP_INFEASIBLE: the cuts are an outer
+    approximation, so the cone programme is infeasible too -- the reference's
+    InSimulationException), or after max_rounds QPs.  A scene that ended keeps the values of
+    the round that ended it, whatever the other scenes of the batch still need.
+
+    ``scene_cells[s]``: the face-record cells of scene s, records [cells, T, 4, 128]."""
+
+    def __init__(self, scene_cells, T, T_full=None, params=None, u_order=U_ORDER_F,
+                 max_rounds=12, tol_g=1e-6, device="cuda", only_violated=False,
+                 car_r=4.47213):
+        if max_rounds < 1:
+            raise ValueError("max_rounds must be >= 1")
+        self.max_rounds, self.tol_g = int(max_rounds), float(tol_g)
+        self.only_violated, self.car_r = bool(only_violated), float(car_r)
+        cells = [int(c) for c in scene_cells]
+        self.qp = PlanningQP([(self.max_rounds + 1) * c for c in cells], T, T_full,
+                             kind=REC_AFFINE_COMPACT, params=params, u_order=u_order,
+                             device=device)
+        dev = self.device = self.qp.device
+        self.S, self.T = self.qp.S, self.qp.T
+        off = np.concatenate(([0], np.cumsum(cells))).astype(np.int64)
+        self.n_cells = int(off[-1])
+        self.scene_cell = torch.as_tensor(off, device=dev)
+        self.pool_cell = self.qp.scene_cell
+        S, T, C = self.S, self.T, self.n_cells
+        self.pool = torch.empty((max(self.qp.n_cells, 1), T, 32), dtype=torch.uint8, device=dev)
+        self.g = torch.empty((max(C, 1), T), dtype=torch.float64, device=dev)
+        self.viol = torch.empty(S, dtype=torch.float64, device=dev)
+        self.state = torch.empty(S, dtype=torch.int32, device=dev)
+        self.u = torch.empty((S, 2 * T), dtype=torch.float64, device=dev)
+        self.X = torch.empty((S, T, 4), dtype=torch.float64, device=dev)
+        self.cost = torch.empty(S, dtype=torch.float64, device=dev)
+
+    def _cuts(self, rec, cell_gamma, face_sel, plan, rnd):
+        engine.face_cuts(rec, self.T, self.scene_cell, self.n_cells, cell_gamma, plan, self.pool,
+                         self.pool_cell, self.g, self.viol, self.state, rnd, self.max_rounds,
+                         self.tol_g, face_sel, self.car_r, self.only_violated)
+
+    def solve(self, gamma, xbar, goal, ref, rec, cell_gamma, plan0, face_sel=None, u_prev=None,
+              ubar=None, ltv=None):
+        """gamma .. ref, u_prev, ubar, ltv: PlanningQP.solve's (ltv rebuilds the model in the
+        first round's launch; the later rounds read what it wrote).  rec: uint8 face records
+        [cells, T, 4, 128]; cell_gamma [cells] float64; plan0 [S, T, >= 2] float64, the point
+        round 0 linearises at (the planner: ref_traj, where approx chose its faces); face_sel
+        int32 [cells, T] or None.  All device tensors.  Returns SocpResult; synchronises once
+        per round."""
+        S = self.S
+        self._cuts(rec, cell_gamma, face_sel, plan0, 0)
+        status = np.full(S, -1, np.int64)
+        rounds = np.zeros(S, np.int64)
+        viol = np.full(S, np.nan)
+        costs = []
+        for rnd in range(1, self.max_rounds + 1):
+            qu, qX, qcost, qstat, _ = self.qp.solve(gamma, xbar, goal, ref, self.pool,
+                                                    u_prev=u_prev, ubar=ubar,
+                                                    ltv=ltv if rnd == 1 else None)
+            self._cuts(rec, cell_gamma, face_sel, qX, rnd)
+            back = torch.stack((self.state.to(torch.float64), qstat.to(torch.float64),
+                                self.viol, qcost)).cpu().numpy()
+            state, qs = back[0].astype(np.int64), back[1].astype(np.int64) & ~QP_SKIPPED_ROWS
+            live = status < 0
+            rounds[live] = rnd
+            costs.append(np.where(live, back[3], np.nan))
+            end = np.full(S, -1, np.int64)
+            end[state == _lib.SOCP_OK] = SOCP_OK
+            if rnd == self.max_rounds:
+                end[state == _lib.SOCP_CUT] = SOCP_MAXROUNDS
+            end[qs == QP_MAXITER] = SOCP_INFEASIBLE
+            end[qs == QP_NUMERIC] = SOCP_NUMERIC
+            end[state >= _lib.SOCP_BAD_ROW] = SOCP_BAD_ROW
+            new = live & (end >= 0)
+            if new.any():
+                idx = torch.as_tensor(np.nonzero(new)[0], device=self.device)
+                self.u[idx] = qu[idx]
+                self.X[idx] = qX[idx]
+                self.cost[idx] = qcost[idx]
+                status[new] = end[new]
+                viol[new] = back[2][new]
+            if (status >= 0).all():
+                break
+        return SocpResult(self.u, self.X, self.cost, status, rounds, viol,
+                          np.array(costs).reshape(-1, S))
 
 
 class PlanningQPStep:

@@ -620,6 +620,8 @@ class MidlevelAgent:
         self.last_records = None
         self._last_rec = None              # (device records, kind, T) of the last generator
         self._audit_src = None             # (scene, K, T, _last_rec or None) of the last graph step
+        self._face_src = None              # (scene, K, T, face records, gamma, rows) of the last
+        #                                    box-face generator (solve_planning_socp's source)
         self._last_sbig = False            # do its rows carry S_big (road boundaries)?
         self._qp_request = None            # the frame's QP inputs, set before its step graph
         self._qp_pending = None            # ((run, gen), records, (T, u_order)) enqueued
@@ -1165,12 +1167,15 @@ class MidlevelAgent:
         self.last_records = h
         self._last_rec = None
         self._audit_src = None
+        self._face_src = None
         mean0 = mean[:, 0, :].cpu().numpy()
         cov0 = cov[:, 0:2, 0:2].cpu().numpy()
         last = mean0[_last_cells(tuple(K))].tolist()             # last mode wins (:1008-1019)
         gate = [not (x >= 190 or y <= -80) for x, y in last]
         cons = FaceConstraintList(h, scene.cell_of, gate, T, gamma, variant,
                                   0.5 * CAR_R)
+        # what solve_planning_socp and audit_face_plan read: the cone rows' own consumers
+        self._face_src = (scene, list(K), T, rec, gamma, cons)
         st_mean, st_cov = self._state_stats(scene, mean0, cov0)
         vertices, A_union, b_union = self._l4_lists(scene)
         return (cons, vertices, A_union, b_union, any(gate), _object_grid(scene.O), st_mean,
@@ -1600,6 +1605,120 @@ class MidlevelAgent:
         rec, kind = (last[0], last[1]) if last is not None else (None, None)
         a = engine.risk_audit(scene.store, plan=plan, rec=rec, rec_kind=kind,
                               R=self.R if R is None else float(R), T=T)
+        return risk.audit_report(a, scene.store.counts, K, self.prediction_horizon)
+
+    def _face_selection(self, cons, C, T, faces):
+        """face_sel [C, T] int32 on the host: -1 for the cells of ungated OVs; for a gated
+        (ov, k, t) approx's own choice, or `faces`: a mapping (ov, k, t) -> face, or an array
+        [gated cells, T] in the constraint list's order (gated OV, mode, t)."""
+        sel = np.full((C, T), -1, np.int32)
+        gated = cons._cells
+        if faces is None:
+            if cons.variant != "approx":
+                raise ValueError(f"the {cons.variant} rows are a disjunction over four faces: "
+                                 "give `faces`, one face per gated (ov, k, t)")
+            for c in gated:
+                for t in range(T):
+                    sel[c, t] = cons.chosen_face(c, t)
+            return sel
+        if isinstance(faces, dict):
+            for c in gated:
+                o, k = cons._cell_of[c]
+                for t in range(T):
+                    if (o, k, t) not in faces:
+                        raise ValueError(f"faces: no face for (ov={o}, k={k}, t={t})")
+                    sel[c, t] = int(faces[(o, k, t)])
+        else:
+            f = np.asarray(faces, np.int64)
+            if f.shape != (len(gated), T):
+                raise ValueError(f"faces must be ({len(gated)}, {T}): one per gated (ov, k, t)")
+            for i, c in enumerate(gated):
+                sel[c] = f[i]
+        if gated and (sel[gated].min() < 0 or sel[gated].max() > 3):
+            raise ValueError("faces must be in 0..3")
+        return sel
+
+    def solve_planning_socp(self, x_init, goal, ref_traj, Tsh, u_prev=None, lon=3.7,
+                            u_order=mpc.U_ORDER_F, faces=None, max_rounds=12, tol_g=1e-6):
+        """The plan under the box-face cone rows of the last box-face generator call: what the
+        reference gets from cvxpy / CPLEX on the approx rows (:1353-1363), here by outer
+        approximation over the planning QP (mpc.PlanningSOCP; the road-boundary slack is 0).
+        Valid after the approx generator, and after nominal / robust when `faces` fixes one face
+        per gated (ov, k, t) (_face_selection); the cells of ungated OVs carry no row.  Round 0
+        linearises at ref_traj, the point approx chose its faces at.  The LTV model is kept as
+        solve_planning_qp keeps it (rebuilt at Tsh == ph, sliced below it with u_prev).
+        Returns solve_planning_qp's dict plus `rounds` and `max_violation`; raises
+        InSimulationException where the programme is infeasible or max_rounds do not reach
+        tol_g, and the record's error where a selected record failed."""
+        if getattr(self, "_face_src", None) is None:
+            raise RuntimeError("no face records: call a box-face generator first")
+        scene, K, T, rec, gamma, cons = self._face_src
+        if int(Tsh) != T:
+            raise ValueError(f"records are for T = {T}, not Tsh = {Tsh}")
+        ph = self.prediction_horizon
+        if T < ph and u_prev is None:
+            raise ValueError(f"Tsh = {T} < ph = {ph} needs u_prev, the controls executed "
+                             "since the first shrinking step (:3186)")
+        C = rec.shape[0]
+        sel = self._face_selection(cons, C, T, faces)
+        if rec.shape[1] != T:               # the store's horizon is longer: the first T steps
+            rec = rec[:, :T].contiguous()
+        dev = self.device
+        key = (C, T, u_order, int(max_rounds), float(tol_g))
+        cache = self.__dict__.setdefault("_socp", {})
+        run = cache.get(key)
+        if run is None:
+            run = cache[key] = mpc.PlanningSOCP([C], T, ph, params=self.mpc_params,
+                                                u_order=u_order, max_rounds=max_rounds,
+                                                tol_g=tol_g, device=dev, car_r=CAR_R)
+        xbar, gam = self._ltv_buffers()
+        build = T == ph or not self._ltv_built
+        f64 = dict(dtype=torch.float64, device=dev)
+        ref = torch.as_tensor(np.asarray(ref_traj, np.float64)[:T, :2].reshape(1, T, 2).copy(),
+                              **f64)
+        x0 = torch.as_tensor(np.asarray(x_init, np.float64).reshape(1, 4), **f64)
+        g2 = torch.as_tensor(np.asarray(goal, np.float64).reshape(1, 2), **f64)
+        up = None if T == ph else torch.as_tensor(
+            np.asarray(u_prev, np.float64).reshape(1, 2 * (ph - T)), **f64)
+        res = run.solve(gam, xbar, g2, ref, rec.reshape(C, T, 4 * 128),
+                        torch.as_tensor(np.asarray(gamma, np.float64), **f64), ref,
+                        face_sel=torch.as_tensor(sel, device=dev), u_prev=up,
+                        ltv=(x0, self.steptime, lon) if build else None)
+        self._ltv_built = True
+        st = int(res.status[0])
+        if st == mpc.SOCP_BAD_ROW:
+            h = self.last_records
+            for c in cons._cells:
+                for t in range(T):
+                    if h["status"][c, t, sel[c, t]] != 0:
+                        o, k = cons._cell_of[c]
+                        raise engine._lib.record_error(
+                            h["status"][c, t, sel[c, t]],
+                            f"face constraint (ov={o}, k={k}, t={t}, face={sel[c, t]})")
+            raise engine._lib.record_error(engine._lib.REC_NONFINITE, "face constraint")
+        if st != mpc.SOCP_OK:
+            raise InSimulationException("Optimizer failed to find a solution")
+        u = res.u[0].cpu().numpy()
+        return {"cost": float(res.cost[0].item()), "U_star": run.qp.U(res.u)[0].cpu().numpy(),
+                "X_star": res.X[0].cpu().numpy(), "goal": np.asarray(goal, np.float64), "u": u,
+                "skipped_rows": False, "rounds": int(res.rounds[0]),
+                "max_violation": float(res.viol[0])}
+
+    def audit_face_plan(self, X_star, R=None):
+        """The plan half of engine.risk_audit on the particles of the last box-face generator
+        call: how many particles of each cell X_star (Tsh, >= 2) passes within R (default: the
+        agent's) of -- the empirical number to set beside audit_plan's for the half-space
+        schemes.  Returns risk.audit_report's dict (no record half: the cone rows are not
+        half-spaces) and changes no planner state."""
+        if getattr(self, "_face_src", None) is None:
+            raise RuntimeError("no face records: call a box-face generator first")
+        scene, K, T, _, _, _ = self._face_src
+        scene.check_live()
+        X = np.asarray(X_star, np.float64)
+        if X.ndim != 2 or X.shape[0] != T or X.shape[1] < 2:
+            raise ValueError(f"X_star must be ({T}, >= 2) for the face step's Tsh = {T}")
+        plan = torch.as_tensor(np.ascontiguousarray(X[None, :, :2]), device=self.device)
+        a = engine.risk_audit(scene.store, plan=plan, R=self.R if R is None else float(R), T=T)
         return risk.audit_report(a, scene.store.counts, K, self.prediction_horizon)
 
     def calibrate_constraints(self, R=None, eps=None, mode=None):

@@ -5,6 +5,7 @@
 #include "ccmpc_common.hpp"
 #include "faces.hpp"
 #include "quantile.hpp"
+#include "socp.hpp"
 
 namespace ccmpc {
 static thread_local std::string g_last_error;
@@ -331,6 +332,35 @@ extern "C" int ccmpc_face_constraints(const void *positions, int dtype, int64_t 
   const int rc = ccmpc::launch_face_constraints(a, n_particles_bound, workspace,
                                                 ccmpc::as_stream(stream));
   CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
+  CCMPC_LAUNCH_CHECK();
+  return CCMPC_OK;
+}
+
+// ---- Outer-approximation cuts of the face rows (socp.hip) -----------------------------------
+extern "C" int ccmpc_face_cuts(const ccmpc_face_rec *rec, int64_t T, int64_t n_scenes,
+                               const int64_t *scene_cell, const int32_t *face_sel,
+                               const double *cell_gamma, double car_r, const double *plan,
+                               int64_t ld_plan, int32_t round, int32_t max_rounds, double tol_g,
+                               int32_t only_violated, ccmpc_gather_rec *pool,
+                               const int64_t *pool_cell, double *out_g, double *out_viol,
+                               int32_t *out_state, ccmpc_stream_t stream) {
+  static_assert(sizeof(ccmpc_gather_rec) == 32, "ccmpc_gather_rec is 32 bytes");
+  CCMPC_REQUIRE(T >= 1 && T <= ccmpc::kCutMaxT, "T must be in [1, 40]");
+  CCMPC_REQUIRE(std::isfinite(tol_g), "tol_g must be finite");
+  CCMPC_REQUIRE(std::isfinite(car_r), "car_r must be finite");
+  CCMPC_REQUIRE(max_rounds >= 0 && max_rounds < (1 << 15), "max_rounds must be in [0, 2^15)");
+  CCMPC_REQUIRE(round >= 0 && round <= max_rounds, "round must be in [0, max_rounds]");
+  CCMPC_REQUIRE(ld_plan >= 2, "ld_plan must be >= 2");
+  CCMPC_REQUIRE(n_scenes >= 0 && n_scenes < (int64_t(1) << 31), "bad n_scenes");
+  CCMPC_REQUIRE(pool && out_g && out_viol && out_state, "null output");
+  CCMPC_REQUIRE(rec && scene_cell && cell_gamma && plan && pool_cell, "null pointer");
+  CCMPC_REQUIRE(ccmpc::aligned(rec, 8) && ccmpc::aligned(pool, 16), "misaligned records");
+  if (n_scenes == 0) return CCMPC_OK;
+  const ccmpc::FaceCutArgs a{rec, static_cast<int>(T), scene_cell, face_sel, cell_gamma, car_r,
+                             plan, ld_plan, round, max_rounds, tol_g, only_violated,
+                             reinterpret_cast<double4 *>(pool), pool_cell, out_g, out_viol,
+                             out_state};
+  ccmpc::launch_face_cuts(a, n_scenes, ccmpc::as_stream(stream));
   CCMPC_LAUNCH_CHECK();
   return CCMPC_OK;
 }

@@ -830,6 +830,82 @@ int ccmpc_face_constraints(const void *positions, int dtype, int64_t ld, int64_t
                            size_t workspace_bytes, ccmpc_face_rec *out_rec, ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Outer-approximation (Kelley) cuts of the box-face cone rows: what turns ccmpc_face_rec rows
+ * into records ccmpc_mpc_qp reads.  The reference hands the rows to cvxpy / CPLEX as
+ * second-order cones (v8ideal/__init__.py:1353-1363); with one face fixed per (cell, t) -- the
+ * approx generator's choice, or the caller's -- each row is convex in the ego position of step t,
+ *   g(x_t) = mean . xi + Gamma |root xi|_2 + 0.5 car_r <= 0,   xi = (X_t, Y_t, 1),
+ * and the plan follows from the strictly convex planning QP over linearisations of g: cut every
+ * row at the current plan, solve the QP over all cuts so far, repeat until max g <= tol_g.  The
+ * cuts are an outer approximation, so a QP that is infeasible in some round certifies that the
+ * cone programme is infeasible.  One call = one round's cuts for every scene, one launch.
+ *
+ *  rec[cells][T][4]   ccmpc_face_constraints' records;  scene s owns cells
+ *                     [scene_cell[s], scene_cell[s+1])  (device, as ccmpc_mpc_qp)
+ *  face_sel[cells][T] 0..3: that face; -1: no row for (cell, t) (an OV outside the junction
+ *                     gate); NULL: the face whose record has chosen == 1
+ *  cell_gamma[cells]  Gamma, as ccmpc_face_constraints;  car_r likewise
+ *  plan[s][T][ld_plan] the point to linearise at: x, y = the first two of each step's ld_plan
+ *                     doubles (ld_plan = 4 reads ccmpc_mpc_qp's out_x in place; ld_plan >= 2)
+ *
+ * A selected record with status != 0, a face_sel outside [-1, 3], and (face_sel == NULL) a
+ * (cell, t) whose records carry CCMPC_FACE_NO_CHOICE or no chosen face make the scene's state
+ * CCMPC_SOCP_BAD_ROW: no cuts are written for it, in this or any later round.
+ *
+ * Arithmetic of a row at p = (x, y) = plan[s][t], float64, no contraction, in this order
+ * (products before sums, sums left to right; root = r00 r01 r02 r11 r12 r22):
+ *   w0 = r00 x + r01 y + r02,  w1 = r01 x + r11 y + r12,  w2 = r02 x + r12 y + r22
+ *   nw = sqrt(w0 w0 + w1 w1 + w2 w2)
+ *   g  = m0 x + m1 y + m2 + Gamma nw + 0.5 car_r
+ *   v0 = r00 w0 + r01 w1 + r02 w2,  v1 = r01 w0 + r11 w1 + r12 w2
+ *   a  = (m0 + Gamma v0 / nw, m1 + Gamma v1 / nw), or (m0, m1) where nw == 0 (a valid subgradient)
+ *   b  = a0 x + a1 y - g
+ * The cut a . x_t <= b is stored as n = a, rhs = b, side = -1, status = 0, t_tau = t.  It
+ * supports g at p (a . p - b = g(p)) and lies below it everywhere (a . q - b <= g(q)).
+ *
+ * Pool: scene s owns pool cells [pool_cell[s], pool_cell[s+1]), which must number
+ * (max_rounds + 1) x the scene's cells: region r = cells [r cells_s, (r + 1) cells_s) of T
+ * records, record t of a cell belonging to step t.  The call with `round` = r writes region r in
+ * full -- a cut or an empty record (status CCMPC_CUT_EMPTY, n = rhs = 0) per (cell, t) -- and the
+ * call with round == 0 also empties every later region: the caller initialises nothing.
+ * ccmpc_mpc_qp reads the pool in place with rec_kind CCMPC_REC_KIND_AFFINE_COMPACT, scene_cell =
+ * pool_cell and max_cells_per_scene = (max_rounds + 1) x the largest scene; it skips the empty
+ * records (and raises CCMPC_QP_SKIPPED_ROWS, which means nothing here).  A scene whose pool
+ * range has another size gets CCMPC_SOCP_BAD_LAYOUT and its pool is not touched.
+ *
+ * Outputs, all written by every call (no initial values needed):
+ *  out_g[cells][T]  g of the selected row; -inf where face_sel is -1, NaN for a bad row
+ *  out_viol[s]      the largest g of the scene's selected rows, -inf if it has none, NaN if a
+ *                   row is bad or some g is NaN
+ *  out_state[s]     sticky: read back by the calls with round > 0.
+ *                   CCMPC_SOCP_CUT      cuts were written (always in round 0, which judges the
+ *                                       linearisation point, not a plan of the programme);
+ *                   CCMPC_SOCP_OK       round > 0 and out_viol[s] <= tol_g: this call and every
+ *                                       later one write only empty records for the scene, so its
+ *                                       QP stays the same problem and returns the same bits;
+ *                   CCMPC_SOCP_BAD_ROW, CCMPC_SOCP_BAD_LAYOUT as above.
+ * only_violated != 0: rounds >= 1 write a cut only for rows with g > 0 (the others cannot
+ * be active at the next plan's neighbourhood; fewer QP rows, possibly more rounds).
+ *
+ * One workgroup of one wave per scene, the maximum reduced in the wave (exact, so no order can
+ * change it), no atomics, no workspace, no host synchronisation: capturable.
+ * CCMPC_ERR_ARG: T outside [1, 40], tol_g or car_r not finite, max_rounds < 0 or >= 2^15, round
+ * outside [0, max_rounds], ld_plan < 2, n_scenes outside [0, 2^31), a NULL pointer other than
+ * face_sel, pool not 16-byte aligned.
+ * ------------------------------------------------------------------------------------- */
+#define CCMPC_SOCP_OK 0
+#define CCMPC_SOCP_CUT 1
+#define CCMPC_SOCP_BAD_ROW 2
+#define CCMPC_SOCP_BAD_LAYOUT 3
+#define CCMPC_CUT_EMPTY 1 /* ccmpc_gather_rec.status of a pool record that holds no cut */
+int ccmpc_face_cuts(const ccmpc_face_rec *rec, int64_t T, int64_t n_scenes,
+                    const int64_t *scene_cell, const int32_t *face_sel, const double *cell_gamma,
+                    double car_r, const double *plan, int64_t ld_plan, int32_t round,
+                    int32_t max_rounds, double tol_g, int32_t only_violated,
+                    ccmpc_gather_rec *pool, const int64_t *pool_cell, double *out_g,
+                    double *out_viol, int32_t *out_state, ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * TEST ONLY (not a reference interface): the half-space tail's device functions -- the ones
  * ccmpc_minkowski_cycle / ccmpc_minkowski / ccmpc_affine_scale run per record -- on n batched
  * inputs, so the reference's component golden vectors reach the device arithmetic.  Device
