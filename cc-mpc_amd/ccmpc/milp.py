@@ -208,7 +208,7 @@ def compute_objective(X, U, goal, objective=None):
 
 
 def v8_qp_params(max_steer_deg=70.0, objective=None, limits=None):
-    """ccmpc_mpc_params of v8's problem for mpc_qp_kernel: v8's objective is the kernel's with
+    """ccmpc_mpc_params of v8's problem for ccmpc_mpc_qp: v8's objective is the kernel's with
     no reference term (w_ref = 0) and R2's off-diagonal w_ch_joint / 2 (v8 adds w_ch_joint
     du_0 du_1 once; the kernel's quadratic form counts its off-diagonal twice); solved with
     CCMPC_U_ORDER_C (U = u.reshape(T, nu) of an object array pairs (u[2t], u[2t+1]))."""
@@ -252,7 +252,7 @@ class RoadSegments:
 
 class MilpBnB:
     """Exact best-first branch and bound of the planner's MILPs on the GPU, around
-    mpc_qp_kernel: every node's relaxation is one convex QP, and each round's nodes are ONE
+    ccmpc_mpc_qp: every node's relaxation is one convex QP, and each round's nodes are ONE
     batched launch.  The binaries it branches on:
 
       faces     v8's Delta: one L4 face a_l . x_t + S_t >= rhs_l per (cell, t) (milp.BigMRows)
@@ -389,7 +389,7 @@ class MilpBnB:
         return rec
 
     def _solve_batch(self, nodes):
-        """One mpc_qp_kernel launch over the nodes: (u, X, cost, ok) host arrays.  The round's
+        """One ccmpc_mpc_qp call over the nodes: (u, X, cost, ok) host arrays.  The round's
         traffic is one pinned pack each way (records, goal, reference and executed controls up
         in one copy kernel; u, X, cost, status down in one, then a polled signal), on buffers
         cached per shape across frames (_RoundIO)."""

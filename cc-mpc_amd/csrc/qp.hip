@@ -18,6 +18,7 @@
 // bitwise reproducible.  Cholesky and both triangular solves run on wave 0 (lane = row),
 // wave-synchronous, with no workgroup barrier per column.
 #include "ccmpc_common.hpp"
+#include "qp_wave.hpp"
 #include <cstdlib>
 #include <cstring>
 
@@ -51,12 +52,6 @@ constexpr double kEarlyPolish = 1e-4;
 constexpr int kQpDefaultMethod = CCMPC_QP_METHOD_GI;
 // internal status bit: the active-set-only instance handed this scene to the IPM pass
 constexpr int kQpNeedIpm = 1 << 20;
-// the records' first loads: 1 = with the setup's first reads (before the model), 0 = in the rows
-// phase, after the model's barrier (which otherwise waits for them: they sit behind the
-// scene-cell load, two dependent round trips)
-#ifndef CCMPC_QP_REC_PREFETCH
-#define CCMPC_QP_REC_PREFETCH 1
-#endif
 
 // ---- the LTV model ---------------------------------------------------------------------------
 // About u = 0 the bicycle model's nominal trajectory is straight at constant speed
@@ -202,6 +197,12 @@ struct QpLayout {
     rows = o;
     const int64_t mrows = 2 * n + 2 * T + R;
     if (rows_lds) o += static_cast<int>(kQpRowDoubles * mrows);
+    // the active-set solve prefetches R's rows 16 wide (n <= 16; 32 above) whatever n is: the
+    // columns >= n are never used, but it reads up to 15 - n entries past R.  pact, pdinv and
+    // the rows behind them cover those except for n < 5 with the rows elsewhere; the image ends
+    // with the rest in reserve, so that no read leaves it (no block's offset depends on it; a
+    // guard per column cost the T = 12 solve 1.2 to 2.5 %, profiles/r19/README.md)
+    if (polish && 3 * n < 15) o += 15 - 3 * n;
     total = o;
   }
 };
@@ -221,323 +222,6 @@ struct Rows {
   int32_t *ix;      // (i0, i1) per row
   double *rp, *is;  // this iteration's primal residual g + s and 1 / s (set in I1)
 };
-
-// Lane moves inside a row of 16 (DPP; f64 as two 32-bit halves).  `old` is what a lane keeps
-// if its source is out of range -- never the case for the controls used here, with the whole
-// wave active (every caller reduces in wave-uniform control flow).
-template <int CTRL>
-__device__ __forceinline__ double qp_dpp(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo =
-      __builtin_amdgcn_update_dpp(0u, static_cast<uint32_t>(u), CTRL, 0xf, 0xf, false);
-  const uint32_t hi =
-      __builtin_amdgcn_update_dpp(0u, static_cast<uint32_t>(u >> 32), CTRL, 0xf, 0xf, false);
-  return __builtin_bit_cast(double, (static_cast<uint64_t>(hi) << 32) | lo);
-}
-constexpr int kDppQuad1 = 0xB1;        // quad_perm [1,0,3,2]
-constexpr int kDppQuad2 = 0x4E;        // quad_perm [2,3,0,1]
-constexpr int kDppHalfMirror = 0x141;  // lane i of 8 <- lane 7-i: the other quad
-constexpr int kDppMirror = 0x140;      // lane i of 16 <- lane 15-i: the other half-row
-
-__device__ __forceinline__ double lane_bcast(double v, int src) {  // src wave-uniform
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(u), src);
-  const uint32_t hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(u >> 32), src);
-  return __builtin_bit_cast(double, (static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-// Sum over each group of 4 / 8 consecutive lanes (every lane of the group gets it)
-__device__ __forceinline__ double sum4(double v) {
-  v += qp_dpp<kDppQuad1>(v);
-  return v + qp_dpp<kDppQuad2>(v);
-}
-__device__ __forceinline__ double sum8(double v) {
-  v = sum4(v);
-  return v + qp_dpp<kDppHalfMirror>(v);
-}
-
-// Whole-wave reductions: four DPP steps reduce each row of 16, then the four row results are
-// combined in a fixed order from lanes 0, 16, 32, 48 (uniform result, no LDS round trips)
-__device__ __forceinline__ double wave_sum(double v) {
-  v = sum8(v);
-  v += qp_dpp<kDppMirror>(v);
-  return (lane_bcast(v, 0) + lane_bcast(v, 16)) + (lane_bcast(v, 32) + lane_bcast(v, 48));
-}
-__device__ __forceinline__ double wave_max(double v) {
-  v = fmax(v, qp_dpp<kDppQuad1>(v));
-  v = fmax(v, qp_dpp<kDppQuad2>(v));
-  v = fmax(v, qp_dpp<kDppHalfMirror>(v));
-  v = fmax(v, qp_dpp<kDppMirror>(v));
-  return fmax(fmax(lane_bcast(v, 0), lane_bcast(v, 16)), fmax(lane_bcast(v, 32), lane_bcast(v, 48)));
-}
-__device__ __forceinline__ double wave_min(double v) {
-  v = fmin(v, qp_dpp<kDppQuad1>(v));
-  v = fmin(v, qp_dpp<kDppQuad2>(v));
-  v = fmin(v, qp_dpp<kDppHalfMirror>(v));
-  v = fmin(v, qp_dpp<kDppMirror>(v));
-  return fmin(fmin(lane_bcast(v, 0), lane_bcast(v, 16)), fmin(lane_bcast(v, 32), lane_bcast(v, 48)));
-}
-
-// Block reductions of up to 2 values (every thread gets the result); two barriers.  NW = 1
-// (one wave per scene): the wave reduction alone, no LDS and no barrier.
-template <int NW>
-__device__ __forceinline__ void block_max2(double &a, double &b, double *red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  a = wave_max(a);
-  b = wave_max(b);
-  if (NW == 1) return;
-  if (lane == 0) {
-    red[2 * w] = a;
-    red[2 * w + 1] = b;
-  }
-  __syncthreads();
-  a = red[0];
-  b = red[1];
-  for (int k = 1; k < NW; ++k) {
-    a = fmax(a, red[2 * k]);
-    b = fmax(b, red[2 * k + 1]);
-  }
-  __syncthreads();
-}
-template <int NW>
-__device__ __forceinline__ double block_sum(double a, double *red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  a = wave_sum(a);
-  if (NW == 1) return a;
-  if (lane == 0) red[w] = a;
-  __syncthreads();
-  a = red[0];
-  for (int k = 1; k < NW; ++k) a += red[k];
-  __syncthreads();
-  return a;
-}
-template <int NW>
-__device__ __forceinline__ double block_min(double a, double *red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  a = wave_min(a);
-  if (NW == 1) return a;
-  if (lane == 0) red[w] = a;
-  __syncthreads();
-  a = red[0];
-  for (int k = 1; k < NW; ++k) a = fmin(a, red[k]);
-  __syncthreads();
-  return a;
-}
-
-// Block argmax (largest value, smallest index on ties); every thread gets the result.
-template <int NW>
-__device__ __forceinline__ void block_argmax(double &v, double &idx, double *red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o, 64), oi = __shfl_xor(idx, o, 64);
-    if (ov > v || (ov == v && oi < idx)) {
-      v = ov;
-      idx = oi;
-    }
-  }
-  if (NW == 1) return;
-  if (lane == 0) {
-    red[2 * w] = v;
-    red[2 * w + 1] = idx;
-  }
-  __syncthreads();
-  v = red[0];
-  idx = red[1];
-  for (int k = 1; k < NW; ++k) {
-    if (red[2 * k] > v || (red[2 * k] == v && red[2 * k + 1] < idx)) {
-      v = red[2 * k];
-      idx = red[2 * k + 1];
-    }
-  }
-  __syncthreads();
-}
-
-
-// wave-level ordering of LDS traffic between the lanes of wave 0 (one wave executes its LDS
-// instructions in order; this keeps the compiler from moving them across the step)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The workgroup's barrier; with one wave per scene, the wave-level ordering above (a wave runs
-// its LDS instructions in order, so every lane then sees every other lane's writes)
-template <int NW>
-__device__ __forceinline__ void qp_sync() {
-  if (NW == 1)
-    wave_sync();
-  else
-    __syncthreads();
-}
-
-// Wave-level dense Cholesky and triangular solves (called by one whole wave; lane = row, two
-// rows per lane, so N <= 128).  A holds the lower triangle, row stride ld; it is overwritten by
-// L, and dinv[j] = 1 / L[j][j].  With pivot_skip a pivot that cancellation drove to <= 0 is
-// replaced by a huge one (see the IPM below); otherwise it fails.  Returns true on failure.
-__device__ bool wave_cholesky(double *A, int N, int ld, double *dinv, bool pivot_skip) {
-  const int lane = threadIdx.x & 63;
-  bool fail = false;
-  for (int j = 0; j < N; ++j) {
-    double sv[2];
-    const double ajj = A[j * ld + j];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int i = j + lane + 64 * h;
-      double v = 0.0;
-      if (i < N) {
-        v = A[i * ld + j];
-        for (int k = 0; k < j; ++k) v -= A[i * ld + k] * A[j * ld + k];
-      }
-      sv[h] = v;
-    }
-    double dj = lane_bcast(sv[0], 0);
-    fail = fail || !isfinite(dj) || !isfinite(ajj);
-    if (!(dj > 1e-30 * ajj)) {
-      fail = fail || !pivot_skip;
-      dj = 1e128;
-    }
-    const double ljj = sqrt(dj), inv = 1.0 / ljj;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int i = j + lane + 64 * h;
-      if (i < N) A[i * ld + j] = (i == j) ? ljj : sv[h] * inv;
-    }
-    if (lane == 0) dinv[j] = inv;
-    wave_sync();
-  }
-  return fail;
-}
-
-// b <- L^{-1} b (b[h] is row lane + 64 h)
-__device__ __forceinline__ void wave_forward(const double *L, int N, int ld, const double *dinv,
-                                             double b[2]) {
-  const int lane = threadIdx.x & 63;
-  for (int j = 0; j < N; ++j) {
-    const double yj = lane_bcast((j >> 6) ? b[1] : b[0], j & 63) * dinv[j];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int i = lane + 64 * h;
-      if (i == j) b[h] = yj;
-      else if (i > j && i < N) b[h] -= L[i * ld + j] * yj;
-    }
-  }
-}
-
-// b <- L^{-T} b
-__device__ __forceinline__ void wave_backward(const double *L, int N, int ld, const double *dinv,
-                                              double b[2]) {
-  const int lane = threadIdx.x & 63;
-  for (int j = N - 1; j >= 0; --j) {
-    const double xj = lane_bcast((j >> 6) ? b[1] : b[0], j & 63) * dinv[j];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int i = lane + 64 * h;
-      if (i == j) b[h] = xj;
-      else if (i < j) b[h] -= L[j * ld + i] * xj;
-    }
-  }
-}
-
-__device__ __forceinline__ void wave_load2(const double *x, int N, double b[2]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) b[h] = (lane + 64 * h < N) ? x[lane + 64 * h] : 0.0;
-}
-__device__ __forceinline__ void wave_store2(double *x, int N, const double b[2]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-    if (lane + 64 * h < N) x[lane + 64 * h] = b[h];
-}
-
-// Register-resident variants for n <= NM (one row per lane of the calling wave): the
-// IPM factors and solves twice per iteration, and with L in registers a column step is a
-// readlane and an FMA instead of a dependent LDS round trip.  a[k] = L[lane][k] (row form),
-// dl = 1 / L[lane][lane]; the L^T solve reads L's rows from LDS (independent of the chain, so
-// the unrolled loads issue ahead of it).  The matrix is padded to NM x NM with the identity
-// (rows and columns >= n; the right-hand side 0 there), so every step runs unconditionally:
-// straight-line code, no per-column branch on a runtime n.
-template <int NM, bool SKIP = true>
-__device__ __forceinline__ bool reg_cholesky(double (&a)[NM], double &dl) {
-  const int lane = threadIdx.x & 63;
-  bool fail = false;
-  double diag0 = 0.0;  // the lane's original diagonal (for the pivot-skip threshold)
-#pragma unroll
-  for (int k = 0; k < NM; ++k)
-    if (k == lane) diag0 = a[k];
-  fail = __ballot(lane < NM && !isfinite(diag0)) != 0;
-#pragma unroll
-  for (int j = 0; j < NM; ++j) {
-    {
-      double d = lane_bcast(a[j], j);
-      // lane j's pivot against its own original diagonal, as a ballot bit (no broadcast)
-      const bool tiny = (__ballot(!(a[j] > 1e-30 * diag0)) >> j) & 1;
-      fail = fail || !isfinite(d);
-      if (tiny) {  // pivot skip (the IPM), or a failure (SKIP = false)
-        fail = fail || !SKIP;
-        d = 1e128;
-      }
-      // sqrt and 1/sqrt from the hardware rsqrt + one Goldschmidt step (~1 ulp; the IPM's
-      // factor needs no IEEE rounding, the polish recomputes the answer from H exactly)
-      const double y = __builtin_amdgcn_rsq(d);
-      double g = d * y, h = 0.5 * y;
-      const double rr = fma(-g, h, 0.5);
-      g = fma(g, rr, g);
-      h = fma(h, rr, h);
-      const double ljj = g, inv = 2.0 * h;
-      const double lij = lane > j ? a[j] * inv : (lane == j ? ljj : 0.0);
-      a[j] = lij;
-      if (lane == j) dl = inv;
-      // trailing update without an exec-mask branch: rows above k pick up values in their
-      // (never read) upper triangle; lij = 0 for rows < j keeps their finished rows intact
-#pragma unroll
-      for (int k = j + 1; k < NM; ++k) a[k] = fma(-lij, lane_bcast(lij, k), a[k]);
-    }
-  }
-  return fail;
-}
-
-// lt[j] = L[j][lane], the L^T solve's column (from L's lower triangle in LDS, row stride ld)
-template <int NM>
-__device__ __forceinline__ void reg_load_lt(const double *L, int ld, int n, double (&lt)[NM]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = 0; j < NM; ++j) {  // every lane loads (in-bounds index), then selects
-    const double v = L[(j < n ? j : 0) * ld + (lane < j ? lane : 0)];
-    lt[j] = (lane < j && j < n) ? v : 0.0;
-  }
-}
-template <int NM>  // b <- L^{-1} b (b on lane = row)
-__device__ __forceinline__ double reg_forward(const double (&a)[NM], double dl, double b) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = 0; j < NM; ++j) {
-    const double yj = lane_bcast(b * dl, j);  // lane j's b is final: one broadcast
-    const double upd = fma(-a[j], yj, b);
-    b = lane == j ? yj : (lane > j ? upd : b);
-  }
-  return b;
-}
-template <int NM>  // b <- L^{-T} b
-__device__ __forceinline__ double reg_backward(const double (&lt)[NM], double dl, double b) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = NM - 1; j >= 0; --j) {
-    const double xj = lane_bcast(b * dl, j);
-    const double upd = fma(-lt[j], xj, b);
-    b = lane == j ? xj : (lane < j ? upd : b);
-  }
-  return b;
-}
-template <int NM>
-__device__ __forceinline__ double reg_solve(const double (&a)[NM], const double *L, int ld,
-                                            double dl, int n, double b) {
-  double lt[NM];  // read ahead of the chain
-  reg_load_lt(L, ld, n, lt);
-  return reg_backward(lt, dl, reg_forward(a, dl, b));
-}
 
 // control index of U_t component c: cp.reshape(u, (T, 2)) is column-major by default
 __device__ __forceinline__ int u_index(int t, int c, int T, int order) {
@@ -586,64 +270,130 @@ __device__ __forceinline__ double hctrl_mul(const double *z, int i, int T, int o
   return acc;
 }
 
-// NW waves per scene: 4 (the general form), or 1 for n = 2T <= 16 (the reference's ph = 8):
-// every barrier is then a wave-level ordering and every reduction a wave butterfly, which
-// takes the ~30 workgroup barriers per IPM iteration off the chain.
-template <bool ROWS_LDS, int NM, int NW, bool GI = false, bool GIONLY = false>
-__global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
-  // multiply-adds fused in the solver (the library builds with -ffp-contract=off for the
-  // moments' reference arithmetic; the IPM's iterates carry no such contract, and its answer
-  // is the verified polish / KKT point, tested against the oracle QP to a tolerance)
-#pragma clang fp contract(fast)
-  constexpr int NTH = 64 * NW;
-  extern __shared__ double lds[];
-  const int64_t sc = blockIdx.x;
-  if (sc >= A.S) return;
-  // the IPM pass after a GIONLY launch solves only the scenes the active-set pass handed over
-  if (A.fallback_only && !(A.out_status[sc] & kQpNeedIpm)) return;
+// H = H_ctrl + sum_t w_t Gs_t^T Gs_t (x and y rows of each step; no barrier terms) into M's
+// lower triangle: what the polish and the active-set solve factor.  One wave with n <= 16 reads
+// the H_ctrl table Hc, lane column jm = lane & 15, rows (lane >> 4) + 4 m, as the IPM's M; the
+// other forms go entry by entry and evaluate hctrl().
+template <int NW, int NM>
+__device__ __forceinline__ void qp_build_hessian(double *M, const double *Gs, const double *Hc,
+                                                 int n, int ldm, int T, int order,
+                                                 const ccmpc_mpc_params &p) {
+#pragma clang fp contract(fast)  // as the kernels that call it
+  const int tid = threadIdx.x, lane = tid & 63;
+  if constexpr (NW == 1 && NM == 16) {
+    const int jm = lane & 15, jc = jm < n ? jm : 0;
+    double hx[8], hy[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int tt = t < T ? t : 0;
+      const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
+      hx[t] = t < T ? wp * Gs[(3 * tt) * n + jc] : 0.0;
+      hy[t] = t < T ? wp * Gs[(3 * tt + 1) * n + jc] : 0.0;
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int im = (lane >> 4) + 4 * m;
+      const bool on = im < n && jm <= im;
+      const int ic = on ? im : 0;
+      double v = Hc[ic * n + jc];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int tt = t < T ? t : 0;
+        v = fma(Gs[(3 * tt) * n + ic], hx[t], fma(Gs[(3 * tt + 1) * n + ic], hy[t], v));
+      }
+      if (on) M[im * ldm + jm] = v;
+    }
+  } else {
+    for (int e = tid; e < n * n; e += 64 * NW) {
+      const int i = e / n, j = e % n;
+      if (j > i) continue;
+      double v = hctrl(i, j, T, order, p);
+      for (int t = 0; t < T; ++t) {
+        const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
+        v += wp * (Gs[(3 * t) * n + i] * Gs[(3 * t) * n + j] +
+                   Gs[(3 * t + 1) * n + i] * Gs[(3 * t + 1) * n + j]);
+      }
+      M[i * ldm + j] = v;
+    }
+  }
+}
+
 #ifdef CCMPC_QP_TRACE
-  const uint64_t tk0 = wall_clock64();
-  uint64_t smark[4] = {};
 #define QS_MARK(i) (smark[i] = wall_clock64())
 #else
 #define QS_MARK(i) ((void)0)
 #endif
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int T = A.T, Tf = A.Tf, Tp = Tf - T;
-  const int64_t c0 = A.scene_cell[sc], ncell = A.scene_cell[sc + 1] - c0;
-  const int P = static_cast<int>(qp_rows_per_cell(T, A.rec_kind));
-  const int64_t R = ncell * P;
-  const QpLayout lay(T, ROWS_LDS ? R : 0, ROWS_LDS, A.polish != 0);
-  const int n = lay.n, T3 = lay.T3, ldm = lay.ldm;
-  const int nbox = 2 * n, nv = 2 * T;
-  const int64_t mrows = nbox + nv + R;
-  double *Gs = lds + lay.gs, *M = lds + lay.m, *Hc = lds + lay.hc, *c3 = lds + lay.c3,
-         *y = lds + lay.y,
-         *yd = lds + lay.yd, *qf = lds + lay.qf, *q = lds + lay.q, *bw = lds + lay.bw,
-         *z = lds + lay.z, *dz = lds + lay.dz, *rd = lds + lay.rd, *rh = lds + lay.rh,
-         *e2 = lds + lay.e2, *lb = lds + lay.lb,
-         *ub = lds + lay.ub, *dinv = lds + lay.dinv, *red = lds + lay.red;
-  double *rbase;
-  if (ROWS_LDS) {
-    rbase = lds + lay.rows;
-  } else {
-    const int64_t mcap = 2 * n + 2 * T + A.max_cells * P;
-    rbase = A.ws + sc * kQpRowDoubles * mcap;
+
+// What the two kernels below share: one scene's view of a launch -- the pointers carved from
+// QpLayout, the row store, the sizes --, built once, with the setup (records, model, rows,
+// initial point), the row evaluators and the output stage.
+// NW waves per scene: 4 (the general form), or 1 (the IPM for n = 2T <= 16, the reference's
+// ph = 8; the active set for n <= 32): every barrier is then a wave-level ordering and every
+// reduction a wave butterfly, which takes the ~30 workgroup barriers per IPM iteration off the
+// chain.  NM > 0: the factor lives in registers, NM per lane of the one wave.
+// Every member function sets the kernels' fp contract itself (multiply-adds fused in the solver:
+// the library builds with -ffp-contract=off for the moments' reference arithmetic; the IPM's
+// iterates carry no such contract, and its answer is the verified polish / KKT point, tested
+// against the oracle QP to a tolerance).
+template <bool ROWS_LDS, int NM, int NW>
+struct QpScene {
+  static_assert(NM == 0 ? NW == 4 : NW == 1, "a register factor (NM > 0) means one wave");
+  static constexpr int NTH = 64 * NW;
+  const QpArgs &A;
+  const ccmpc_mpc_params &p;
+  double *lds;
+  int64_t sc, c0, ncell, R, mrows;
+  int tid, lane, w, T, Tf, Tp, P, n, T3, ldm, nbox, nv, order, ncol;
+  QpLayout lay;
+  double *Gs, *M, *Hc, *c3, *y, *yd, *qf, *q, *bw, *z, *dz, *rd, *rh, *e2, *lb, *ub, *dinv, *red;
+  Rows rw;
+  const double *oa0, *oa1;  // the obstacle rows' a0, a1 (by obstacle row o = r - nbox - nv)
+  const double *Gam, *xb, *ubar, *uprev, *ref;
+  double g0, g1;
+  int skipped = 0;      // a record was unusable (setup)
+  double tol_p, tol_d;  // the tolerances scaled by the right-hand sides and by f (setup)
+#ifdef CCMPC_QP_TRACE
+  uint64_t tk0, smark[4] = {};
+#endif
+
+  __device__ __forceinline__ QpScene(const QpArgs &A_, double *lds_)
+      : A(A_), p(A_.p), lds(lds_), sc(blockIdx.x), c0(A_.scene_cell[sc]),
+        ncell(A_.scene_cell[sc + 1] - c0), tid(threadIdx.x), lane(tid & 63), w(tid >> 6),
+        T(A_.T), Tf(A_.Tf), Tp(Tf - T), P(static_cast<int>(qp_rows_per_cell(T, A_.rec_kind))),
+        lay(T, ROWS_LDS ? ncell * P : 0, ROWS_LDS, A_.polish != 0) {
+#ifdef CCMPC_QP_TRACE
+    tk0 = wall_clock64();
+#endif
+    R = ncell * P, n = lay.n, T3 = lay.T3, ldm = lay.ldm;
+    nbox = 2 * n, nv = 2 * T, mrows = nbox + nv + R;
+    Gs = lds + lay.gs, M = lds + lay.m, Hc = lds + lay.hc, c3 = lds + lay.c3, y = lds + lay.y;
+    yd = lds + lay.yd, qf = lds + lay.qf, q = lds + lay.q, bw = lds + lay.bw, z = lds + lay.z;
+    dz = lds + lay.dz, rd = lds + lay.rd, rh = lds + lay.rh, e2 = lds + lay.e2;
+    lb = lds + lay.lb, ub = lds + lay.ub, dinv = lds + lay.dinv, red = lds + lay.red;
+    double *rbase;
+    if (ROWS_LDS) {
+      rbase = lds + lay.rows;
+    } else {
+      const int64_t mcap = 2 * n + 2 * T + A.max_cells * P;
+      rbase = A.ws + sc * kQpRowDoubles * mcap;
+    }
+    rw = Rows{rbase, rbase + mrows, rbase + 2 * mrows, rbase + 3 * mrows, rbase + 4 * mrows,
+              rbase + 5 * mrows, rbase + 6 * mrows,
+              reinterpret_cast<int32_t *>(rbase + 7 * mrows), rbase + 8 * mrows,
+              rbase + 9 * mrows};
+    oa0 = rw.c0 + nbox + nv, oa1 = rw.c1 + nbox + nv;
+    order = A.u_order;
+    ncol = 2 * Tf;
+    Gam = A.gamma + sc * (4 * Tf) * ncol;
+    xb = A.xbar + sc * 4 * Tf;
+    ubar = A.ubar ? A.ubar + sc * ncol : nullptr;
+    uprev = (A.u_prev && Tp > 0) ? A.u_prev + sc * 2 * Tp : nullptr;
+    g0 = A.goal[2 * sc], g1 = A.goal[2 * sc + 1];
+    ref = A.ref + sc * 2 * A.n_ref;
   }
-  const Rows rw{rbase,
-                rbase + mrows,
-                rbase + 2 * mrows,
-                rbase + 3 * mrows,
-                rbase + 4 * mrows,
-                rbase + 5 * mrows,
-                rbase + 6 * mrows,
-                reinterpret_cast<int32_t *>(rbase + 7 * mrows),
-                rbase + 8 * mrows,
-                rbase + 9 * mrows};
-  // the obstacle rows' a0, a1 (indexed by obstacle row o = r - nbox - nv)
-  const double *oa0 = rw.c0 + nbox + nv, *oa1 = rw.c1 + nbox + nv;
   // step t of obstacle row o (records of a cell in (t, tau) order, or one per t for affine)
-  auto obst_step = [&](int64_t o) -> int {
+  __device__ __forceinline__ int obst_step(int64_t o) const {
+#pragma clang fp contract(fast)
     const int64_t cell = o / P;
     const int pp = static_cast<int>(o - cell * P);
     if (A.rec_kind != CCMPC_REC_KIND_HALFSPACE) return pp;
@@ -651,30 +401,17 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     while (t * (t - 1) / 2 > pp) --t;
     while ((t + 1) * t / 2 <= pp) ++t;
     return t;
-  };
-  const ccmpc_mpc_params &p = A.p;
-  const int order = A.u_order;
-  const int ncol = 2 * Tf;
-  const double *Gam = A.gamma + sc * (4 * Tf) * ncol;
-  const double *xb = A.xbar + sc * 4 * Tf;
-  const double *ubar = A.ubar ? A.ubar + sc * ncol : nullptr;
-  const double *uprev = (A.u_prev && Tp > 0) ? A.u_prev + sc * 2 * Tp : nullptr;
-  const double g0 = A.goal[2 * sc], g1 = A.goal[2 * sc + 1];
-  const double *ref = A.ref + sc * 2 * A.n_ref;
+  }
   // output row k = 3t + a of the selected state rows: x, y, v of step t (state index 0, 1, 3)
-  auto grow = [&](int k) { return 4 * (Tp + k / 3) + (k % 3 == 2 ? 3 : k % 3); };
+  __device__ __forceinline__ int grow(int k) const {
+    return 4 * (Tp + k / 3) + (k % 3 == 2 ? 3 : k % 3);
+  }
 
-  // ---- setup -------------------------------------------------------------------------------
-  // The records (fresh from the cycle kernel, so cold) and the reference points are loaded
-  // first, with the model's own reads below, so the setup waits for one round trip of global
-  // loads instead of one per phase: the first kRecPre records of every thread in registers
-  // (n0 n1 as one 16-byte load, then d and side / status / t_tau)
-  constexpr int kRecPre = 4;
   struct RecIn {
     double2 nn;
     int4 a, b;  // full records: d at a.xy (offset 16 or 32), b = bytes 112..127; compact: a
   };
-  auto load_rec = [&](int64_t r) -> RecIn {
+  __device__ __forceinline__ RecIn load_rec(int64_t r) const {
     const unsigned char *rec = A.rec + (c0 * P + r) * (A.rec_compact ? 32 : 128);
     RecIn v;
     v.nn = *reinterpret_cast<const double2 *>(rec);
@@ -687,221 +424,717 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
       v.b = *reinterpret_cast<const int4 *>(rec + 112);
     }
     return v;
-  };
-  RecIn rpre[kRecPre];
-#if CCMPC_QP_REC_PREFETCH
-#pragma unroll
-  for (int j = 0; j < kRecPre; ++j) {
-    const int64_t r = tid + static_cast<int64_t>(j) * NTH;
-    if (r < R) rpre[j] = load_rec(r);
   }
-#endif
-  double ref_k = 0.0;  // the reference point entry of qf's first row k = tid
-  if (tid < T3 && tid % 3 < 2) {
-    const int t = tid / 3, tr = t < A.n_ref ? t : A.n_ref - 1;
-    ref_k = ref[2 * tr + tid % 3];
-  }
-  // Gamma's rows in batches of kGsPre loads per thread, every load of a batch issued before
-  // its LDS stores (a store between two loads made each load a round trip of its own: ~6 us
-  // of the one-wave setup at T = 8, where one batch covers all 384 entries)
-  constexpr int kGsPre = 6;
-  if (A.ltv_x0) {
-    // the fused LTV rebuild: this scene's model into the caller's buffers (later frames read
-    // them), Gs and the constant part straight from the model
-    const LtvModel lm(A.ltv_x0 + 4 * sc, A.ltv_Ts, A.ltv_lr, A.ltv_L);
-    const int gr4 = 4 * Tf;
-    double *og = A.ltv_gamma + sc * gr4 * ncol, *ox = A.ltv_xbar + sc * gr4;
-    for (int e = tid; e < gr4 * ncol; e += NTH) og[e] = lm.gamma(e / ncol, e % ncol);
-    for (int r = tid; r < gr4; r += NTH) ox[r] = lm.xbar(r);
-    for (int e = tid; e < T3 * n; e += NTH) Gs[e] = lm.gamma(grow(e / n), 2 * Tp + e % n);
-    for (int k = tid; k < T3; k += NTH) {
-      const int r = grow(k);
-      double c = lm.xbar(r);
-      if (uprev)
-        for (int j = 0; j < 2 * Tp; ++j) c += lm.gamma(r, j) * uprev[j];
-      if (ubar)
-        for (int j = 0; j < n; ++j) c -= lm.gamma(r, 2 * Tp + j) * ubar[2 * Tp + j];
-      c3[k] = c;
-      y[k] = 0.0;
-    }
-  } else {
-  for (int e0 = tid; e0 < T3 * n; e0 += kGsPre * NTH) {
-    double gv[kGsPre];
-#pragma unroll
-    for (int q = 0; q < kGsPre; ++q) {
-      const int e = e0 + q * NTH, ee = e < T3 * n ? e : 0;
-      gv[q] = Gam[static_cast<int64_t>(grow(ee / n)) * ncol + 2 * Tp + ee % n];
-    }
-#pragma unroll
-    for (int q = 0; q < kGsPre; ++q)
-      if (e0 + q * NTH < T3 * n) Gs[e0 + q * NTH] = gv[q];
-  }
-  for (int k = tid; k < T3; k += NTH) {
-    // constant part of the state: x_bar + Gamma_p u_prev - Gamma_f u_bar (:2877-2891)
-    const int r = grow(k);
-    const double *gr = Gam + static_cast<int64_t>(r) * ncol;
-    double c = xb[r];
-    if (uprev) {
-#pragma unroll 8
-      for (int j = 0; j < 2 * Tp; ++j) c += gr[j] * uprev[j];
-    }
-    if (ubar) {
-#pragma unroll 8
-      for (int j = 0; j < n; ++j) c -= gr[2 * Tp + j] * ubar[2 * Tp + j];
-    }
-    c3[k] = c;
-    y[k] = 0.0;
-  }
-  }
-  for (int j = tid; j < n; j += NTH) {
-    // min_u / max_u = vstack((full(T, a), full(T, delta))).T.ravel() (:2874-2875): the bounds
-    // interleave (accel, steer) per step like Gamma's columns, whatever U's reshape order
-    const int c = j & 1;
-    ub[j] = c == 0 ? p.max_a : p.max_delta;
-    lb[j] = c == 0 ? p.min_a : -p.max_delta;
-    z[j] = 0.0;
-  }
-  if constexpr (NW == 1 && NM == 16)  // n <= 16, where the layout reserves the table
-    for (int e = tid; e < n * n; e += NTH) Hc[e] = hctrl(e / n, e % n, T, order, p);
-  qp_sync<NW>();
-  QS_MARK(0);
-  for (int k = tid; k < T3; k += NTH) {
-    // objective's linear term in output space: 2 (w_ref (c - ref_t) + [t = T-1] w_final (c - g))
-    const int t = k / 3, a = k % 3;
-    double v = 0.0;
-    if (a < 2) {
-      const int tr = t < A.n_ref ? t : A.n_ref - 1;
-      v = 2.0 * p.w_ref * (c3[k] - (k == tid ? ref_k : ref[2 * tr + a]));
-      if (t == T - 1) v += 2.0 * p.w_final * (c3[k] - (a == 0 ? g0 : g1));
-    }
-    qf[k] = v;
-  }
-  // obstacle rows: a . (y_xy + c_xy) <= b  ->  a . y_xy <= b' = b - a . c_xy
-  int skipped = 0;
-  double hmax = 0.0;
-  auto obstacle_row = [&](int64_t r, const RecIn &ri) {
-    const double n0 = ri.nn.x, n1 = ri.nn.y;
-    const double d = __builtin_bit_cast(
-        double, (static_cast<uint64_t>(static_cast<uint32_t>(ri.a.y)) << 32) |
-                    static_cast<uint32_t>(ri.a.x));
-    int side, status, tt;
-    if (A.rec_compact) {  // ccmpc_gather_rec: the same fields, packed (int16 side, status)
-      side = static_cast<int16_t>(ri.a.z & 0xFFFF);
-      status = static_cast<int16_t>(static_cast<uint32_t>(ri.a.z) >> 16);
-      tt = ri.a.w;
-    } else {
-      side = ri.b.y;
-      status = ri.b.z;
-      tt = ri.b.w;
-    }
-    const int t = A.rec_kind == CCMPC_REC_KIND_HALFSPACE ? tt >> 16 : tt;
-    const bool ok = status == 0 && isfinite(n0) && isfinite(n1) && isfinite(d) && t >= 0 &&
-                    t < T && (side == 1 || side == -1);
-    double a0 = 0.0, a1 = 0.0, b = 1.0;
-    if (ok) {
-      // side +1: n . x >= d  ->  -n . x <= -d ;  side -1: n . x <= d  (:926-939, :1503-1515)
-      a0 = side == 1 ? -n0 : n0;
-      a1 = side == 1 ? -n1 : n1;
-      b = (side == 1 ? -d : d) - (a0 * c3[3 * t] + a1 * c3[3 * t + 1]);
-    } else {
-      skipped = 1;
-    }
-    const int64_t ro = nbox + nv + r;
-    const int ts = obst_step(r);
-    rw.c0[ro] = a0;
-    rw.c1[ro] = a1;
-    rw.cst[ro] = -b;
-    rw.ix[2 * ro] = 3 * ts;
-    rw.ix[2 * ro + 1] = 3 * ts + 1;
-    hmax = fmax(hmax, fabs(b));
-  };
-#if !CCMPC_QP_REC_PREFETCH
-#pragma unroll
-  for (int j = 0; j < kRecPre; ++j) {
-    const int64_t r = tid + static_cast<int64_t>(j) * NTH;
-    if (r < R) rpre[j] = load_rec(r);
-  }
-#endif
-#pragma unroll
-  for (int j = 0; j < kRecPre; ++j) {
-    const int64_t r = tid + static_cast<int64_t>(j) * NTH;
-    if (r < R) obstacle_row(r, rpre[j]);
-  }
-  for (int64_t r = tid + static_cast<int64_t>(kRecPre) * NTH; r < R; r += NTH)
-    obstacle_row(r, load_rec(r));
-  for (int r = tid; r < nbox + nv; r += NTH) {  // box and speed rows
-    const bool lo = r & 1;
-    int i0;
-    double cst;
-    if (r < nbox) {
-      const int j = r >> 1;
-      i0 = T3 + j;
-      cst = lo ? lb[j] : -ub[j];
-    } else {
-      const int t = (r - nbox) >> 1;
-      i0 = 3 * t + 2;
-      cst = lo ? -c3[3 * t + 2] : c3[3 * t + 2] - p.max_v;
-    }
-    rw.c0[r] = lo ? -1.0 : 1.0;
-    rw.c1[r] = 0.0;
-    rw.cst[r] = cst;
-    rw.ix[2 * r] = i0;
-    rw.ix[2 * r + 1] = i0;
-  }
-  qp_sync<NW>();
-  QS_MARK(1);
-  // f = Gs^T qf (the scaling of the dual residual; kept in LDS for the polish)
-  double fmax_ = 0.0;
-  if constexpr (NW == 1 && NM == 16) {  // a quad per control, DPP sum (as the IPM's rd)
-    const int j = lane >> 2, kq = lane & 3, jj = j < n ? j : 0;
-    double v = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int k = kq + 4 * i, kk = k < T3 ? k : 0;
-      const double g = Gs[kk * n + jj], qk = qf[kk];
-      v = k < T3 ? fma(g, qk, v) : v;
-    }
-    v = sum4(v);
-    if (kq == 0 && j < n) lds[lay.f + j] = v;
-    fmax_ = j < n ? fabs(v) : 0.0;
-  } else {
-    for (int j = tid; j < n; j += NTH) {
-      double v = 0.0;
-      for (int k = 0; k < T3; ++k) v += Gs[k * n + j] * qf[k];
-      lds[lay.f + j] = v;
-      fmax_ = fmax(fmax_, fabs(v));
-    }
-  }
-  QS_MARK(2);
-  // initial point: z = 0 (inside the control box), s = max(-g(0), 1), lambda = 1
+
   // g(z) = row_lin(r, Gs z, z) + row_const(r): the linear part in the state's output rows
   // yy = Gs z (or in z itself for the control bounds), constants folded into b' and the bounds
   // (zz is yy + T3 in every caller: the pairs (y, z), (yd, dz) sit back to back)
-  auto row_lin = [&](int64_t r, const double *yy, const double *zz) -> double {
+  __device__ __forceinline__ double row_lin(int64_t r, const double *yy, const double *zz) const {
+#pragma clang fp contract(fast)
     (void)zz;
     const int2 ix = reinterpret_cast<const int2 *>(rw.ix)[r];
     return rw.c0[r] * yy[ix.x] + rw.c1[r] * yy[ix.y];
-  };
-  auto row_const = [&](int64_t r) -> double { return rw.cst[r]; };
-  auto row_g = [&](int64_t r, const double *yy, const double *zz) -> double {
+  }
+  __device__ __forceinline__ double row_const(int64_t r) const { return rw.cst[r]; }
+  __device__ __forceinline__ double row_g(int64_t r, const double *yy, const double *zz) const {
+#pragma clang fp contract(fast)
     return row_lin(r, yy, zz) + row_const(r);
-  };
+  }
   // Directional derivative of g along dz, given yd = Gs dz.  It must be the linear part
   // itself, never g(dz) - const: near the solution lambda ds / s amplifies any rounding in ds
   // by lambda / s, and an error here that the normal equations did not see leaves a dual
   // residual the iteration can no longer remove.
-  auto row_gd = [&](int64_t r, const double *ydd, const double *dzz) -> double {
+  __device__ __forceinline__ double row_gd(int64_t r, const double *ydd, const double *dzz) const {
     return row_lin(r, ydd, dzz);
-  };
-  for (int64_t r = tid; r < mrows; r += NTH) {
-    const double g = row_g(r, y, z);
-    rw.s[r] = fmax(-g, 1.0);
-    rw.l[r] = 1.0;
-    if (r < nbox + nv) hmax = fmax(hmax, fabs(g));  // bounds' right-hand sides (z = y = 0)
   }
-  block_max2<NW>(hmax, fmax_, red);
-  QS_MARK(3);
-  const double tol_p = A.tol * (1.0 + hmax), tol_d = A.tol * (1.0 + fmax_);
+
+  // ---- setup -------------------------------------------------------------------------------
+  // The records (fresh from the cycle kernel, so cold) and the reference points are loaded
+  // first, with the model's own reads below, so the setup waits for one round trip of global
+  // loads instead of one per phase: the first kRecPre records of every thread in registers
+  // (n0 n1 as one 16-byte load, then d and side / status / t_tau) -- here, not in the rows phase
+  // after the model's barrier, which would otherwise wait for them: they sit behind the
+  // scene-cell load, two dependent round trips
+  __device__ __forceinline__ void setup() {
+#pragma clang fp contract(fast)
+    constexpr int kRecPre = 4;
+    RecIn rpre[kRecPre];
+#pragma unroll
+    for (int j = 0; j < kRecPre; ++j) {
+      const int64_t r = tid + static_cast<int64_t>(j) * NTH;
+      if (r < R) rpre[j] = load_rec(r);
+    }
+    double ref_k = 0.0;  // the reference point entry of qf's first row k = tid
+    if (tid < T3 && tid % 3 < 2) {
+      const int t = tid / 3, tr = t < A.n_ref ? t : A.n_ref - 1;
+      ref_k = ref[2 * tr + tid % 3];
+    }
+    // Gamma's rows in batches of kGsPre loads per thread, every load of a batch issued before
+    // its LDS stores (a store between two loads made each load a round trip of its own: ~6 us
+    // of the one-wave setup at T = 8, where one batch covers all 384 entries)
+    constexpr int kGsPre = 6;
+    if (A.ltv_x0) {
+      // the fused LTV rebuild: this scene's model into the caller's buffers (later frames read
+      // them), Gs and the constant part straight from the model
+      const LtvModel lm(A.ltv_x0 + 4 * sc, A.ltv_Ts, A.ltv_lr, A.ltv_L);
+      const int gr4 = 4 * Tf;
+      double *og = A.ltv_gamma + sc * gr4 * ncol, *ox = A.ltv_xbar + sc * gr4;
+      for (int e = tid; e < gr4 * ncol; e += NTH) og[e] = lm.gamma(e / ncol, e % ncol);
+      for (int r = tid; r < gr4; r += NTH) ox[r] = lm.xbar(r);
+      for (int e = tid; e < T3 * n; e += NTH) Gs[e] = lm.gamma(grow(e / n), 2 * Tp + e % n);
+      for (int k = tid; k < T3; k += NTH) {
+        const int r = grow(k);
+        double c = lm.xbar(r);
+        if (uprev)
+          for (int j = 0; j < 2 * Tp; ++j) c += lm.gamma(r, j) * uprev[j];
+        if (ubar)
+          for (int j = 0; j < n; ++j) c -= lm.gamma(r, 2 * Tp + j) * ubar[2 * Tp + j];
+        c3[k] = c;
+        y[k] = 0.0;
+      }
+    } else {
+    for (int e0 = tid; e0 < T3 * n; e0 += kGsPre * NTH) {
+      double gv[kGsPre];
+#pragma unroll
+      for (int q = 0; q < kGsPre; ++q) {
+        const int e = e0 + q * NTH, ee = e < T3 * n ? e : 0;
+        gv[q] = Gam[static_cast<int64_t>(grow(ee / n)) * ncol + 2 * Tp + ee % n];
+      }
+#pragma unroll
+      for (int q = 0; q < kGsPre; ++q)
+        if (e0 + q * NTH < T3 * n) Gs[e0 + q * NTH] = gv[q];
+    }
+    for (int k = tid; k < T3; k += NTH) {
+      // constant part of the state: x_bar + Gamma_p u_prev - Gamma_f u_bar (:2877-2891)
+      const int r = grow(k);
+      const double *gr = Gam + static_cast<int64_t>(r) * ncol;
+      double c = xb[r];
+      if (uprev) {
+#pragma unroll 8
+        for (int j = 0; j < 2 * Tp; ++j) c += gr[j] * uprev[j];
+      }
+      if (ubar) {
+#pragma unroll 8
+        for (int j = 0; j < n; ++j) c -= gr[2 * Tp + j] * ubar[2 * Tp + j];
+      }
+      c3[k] = c;
+      y[k] = 0.0;
+    }
+    }
+    for (int j = tid; j < n; j += NTH) {
+      // min_u / max_u = vstack((full(T, a), full(T, delta))).T.ravel() (:2874-2875): the bounds
+      // interleave (accel, steer) per step like Gamma's columns, whatever U's reshape order
+      const int c = j & 1;
+      ub[j] = c == 0 ? p.max_a : p.max_delta;
+      lb[j] = c == 0 ? p.min_a : -p.max_delta;
+      z[j] = 0.0;
+    }
+    if constexpr (NM == 16)  // n <= 16, where the layout reserves the table
+      for (int e = tid; e < n * n; e += NTH) Hc[e] = hctrl(e / n, e % n, T, order, p);
+    qp_sync<NW>();
+    QS_MARK(0);
+    for (int k = tid; k < T3; k += NTH) {
+      // objective's linear term in output space: 2 (w_ref (c - ref_t) + [t = T-1] w_final (c - g))
+      const int t = k / 3, a = k % 3;
+      double v = 0.0;
+      if (a < 2) {
+        const int tr = t < A.n_ref ? t : A.n_ref - 1;
+        v = 2.0 * p.w_ref * (c3[k] - (k == tid ? ref_k : ref[2 * tr + a]));
+        if (t == T - 1) v += 2.0 * p.w_final * (c3[k] - (a == 0 ? g0 : g1));
+      }
+      qf[k] = v;
+    }
+    // obstacle rows: a . (y_xy + c_xy) <= b  ->  a . y_xy <= b' = b - a . c_xy
+    double hmax = 0.0;
+    auto obstacle_row = [&](int64_t r, const RecIn &ri) {
+      const double n0 = ri.nn.x, n1 = ri.nn.y;
+      const double d = __builtin_bit_cast(
+          double, (static_cast<uint64_t>(static_cast<uint32_t>(ri.a.y)) << 32) |
+                      static_cast<uint32_t>(ri.a.x));
+      int side, status, tt;
+      if (A.rec_compact) {  // ccmpc_gather_rec: the same fields, packed (int16 side, status)
+        side = static_cast<int16_t>(ri.a.z & 0xFFFF);
+        status = static_cast<int16_t>(static_cast<uint32_t>(ri.a.z) >> 16);
+        tt = ri.a.w;
+      } else {
+        side = ri.b.y;
+        status = ri.b.z;
+        tt = ri.b.w;
+      }
+      const int t = A.rec_kind == CCMPC_REC_KIND_HALFSPACE ? tt >> 16 : tt;
+      const bool ok = status == 0 && isfinite(n0) && isfinite(n1) && isfinite(d) && t >= 0 &&
+                      t < T && (side == 1 || side == -1);
+      double a0 = 0.0, a1 = 0.0, b = 1.0;
+      if (ok) {
+        // side +1: n . x >= d  ->  -n . x <= -d ;  side -1: n . x <= d  (:926-939, :1503-1515)
+        a0 = side == 1 ? -n0 : n0;
+        a1 = side == 1 ? -n1 : n1;
+        b = (side == 1 ? -d : d) - (a0 * c3[3 * t] + a1 * c3[3 * t + 1]);
+      } else {
+        skipped = 1;
+      }
+      const int64_t ro = nbox + nv + r;
+      const int ts = obst_step(r);
+      rw.c0[ro] = a0;
+      rw.c1[ro] = a1;
+      rw.cst[ro] = -b;
+      rw.ix[2 * ro] = 3 * ts;
+      rw.ix[2 * ro + 1] = 3 * ts + 1;
+      hmax = fmax(hmax, fabs(b));
+    };
+#pragma unroll
+    for (int j = 0; j < kRecPre; ++j) {
+      const int64_t r = tid + static_cast<int64_t>(j) * NTH;
+      if (r < R) obstacle_row(r, rpre[j]);
+    }
+    for (int64_t r = tid + static_cast<int64_t>(kRecPre) * NTH; r < R; r += NTH)
+      obstacle_row(r, load_rec(r));
+    for (int r = tid; r < nbox + nv; r += NTH) {  // box and speed rows
+      const bool lo = r & 1;
+      int i0;
+      double cst;
+      if (r < nbox) {
+        const int j = r >> 1;
+        i0 = T3 + j;
+        cst = lo ? lb[j] : -ub[j];
+      } else {
+        const int t = (r - nbox) >> 1;
+        i0 = 3 * t + 2;
+        cst = lo ? -c3[3 * t + 2] : c3[3 * t + 2] - p.max_v;
+      }
+      rw.c0[r] = lo ? -1.0 : 1.0;
+      rw.c1[r] = 0.0;
+      rw.cst[r] = cst;
+      rw.ix[2 * r] = i0;
+      rw.ix[2 * r + 1] = i0;
+    }
+    qp_sync<NW>();
+    QS_MARK(1);
+    // f = Gs^T qf (the scaling of the dual residual; kept in LDS for the polish)
+    double fmax_ = 0.0;
+    if constexpr (NM == 16) {  // a quad per control, DPP sum (as the IPM's rd)
+      const int j = lane >> 2, kq = lane & 3, jj = j < n ? j : 0;
+      double v = 0.0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const int k = kq + 4 * i, kk = k < T3 ? k : 0;
+        const double g = Gs[kk * n + jj], qk = qf[kk];
+        v = k < T3 ? fma(g, qk, v) : v;
+      }
+      v = sum4(v);
+      if (kq == 0 && j < n) lds[lay.f + j] = v;
+      fmax_ = j < n ? fabs(v) : 0.0;
+    } else {
+      for (int j = tid; j < n; j += NTH) {
+        double v = 0.0;
+        for (int k = 0; k < T3; ++k) v += Gs[k * n + j] * qf[k];
+        lds[lay.f + j] = v;
+        fmax_ = fmax(fmax_, fabs(v));
+      }
+    }
+    QS_MARK(2);
+    // initial point: z = 0 (inside the control box), s = max(-g(0), 1), lambda = 1
+    for (int64_t r = tid; r < mrows; r += NTH) {
+      const double g = row_g(r, y, z);
+      rw.s[r] = fmax(-g, 1.0);
+      rw.l[r] = 1.0;
+      if (r < nbox + nv) hmax = fmax(hmax, fabs(g));  // bounds' right-hand sides (z = y = 0)
+    }
+    block_max2<NW>(hmax, fmax_, red);
+    QS_MARK(3);
+    tol_p = A.tol * (1.0 + hmax), tol_d = A.tol * (1.0 + fmax_);
+  }
+
+  // ---- outputs: u, X = Gamma_f u + const (all four state rows), the objective value ----------
+  __device__ __forceinline__ void output(int status, int it) {
+#pragma clang fp contract(fast)
+    for (int j = tid; j < n; j += NTH) A.out_u[sc * n + j] = z[j];
+    double part = 0.0;
+    for (int r = tid; r < 4 * T; r += NTH) {
+      const int gr = 4 * Tp + r;
+      const double *g = Gam + static_cast<int64_t>(gr) * ncol;
+      double x = xb[gr];
+      if (uprev)
+        for (int j = 0; j < 2 * Tp; ++j) x += g[j] * uprev[j];
+      for (int j = 0; j < n; ++j) x += g[2 * Tp + j] * (z[j] - (ubar ? ubar[2 * Tp + j] : 0.0));
+      A.out_x[sc * 4 * T + r] = x;
+      const int t = r / 4, a = r % 4;
+      if (a < 2) {  // compute_objective_referenceTraj (:2478-2507) at the solution
+        const int tr = t < A.n_ref ? t : A.n_ref - 1;
+        const double e = x - ref[2 * tr + a];
+        part += p.w_ref * e * e;
+        if (t == T - 1) {
+          const double ef = x - (a == 0 ? g0 : g1);
+          part += p.w_final * ef * ef;
+        }
+      }
+    }
+    for (int t = tid; t < T; t += NTH) {
+      const double a0 = z[u_index(t, 0, T, order)], a1 = z[u_index(t, 1, T, order)];
+      part += a0 * (p.w_accel * a0 + p.w_joint * a1) + a1 * (p.w_joint * a0 + p.w_turning * a1);
+      if (t >= 1) {
+        const double d0 = a0 - z[u_index(t - 1, 0, T, order)];
+        const double d1 = a1 - z[u_index(t - 1, 1, T, order)];
+        part += d0 * (p.w_ch_accel * d0 + p.w_ch_joint * d1) +
+                d1 * (p.w_ch_joint * d0 + p.w_ch_turning * d1);
+      }
+    }
+    const double cost = block_sum<NW>(part, red);
+    double sk = skipped;
+    double dummy = 0.0;
+    block_max2<NW>(sk, dummy, red);
+    if (tid == 0) {
+      A.out_cost[sc] = cost;
+      A.out_status[sc] = status | (sk > 0.0 ? CCMPC_QP_SKIPPED_ROWS : 0);
+      A.out_iter[sc] = it;
+    }
+  }
+};
+
+// ---- Goldfarb-Idnani dual active-set solve (one wave, n <= NM = 16 or 32; CCMPC_QP_METHOD_GI)
+template <bool ROWS_LDS, int NM>
+__global__ __launch_bounds__(64) void mpc_qp_gi_kernel(QpArgs A) {
+#pragma clang fp contract(fast)  // see QpScene
+  static_assert(NM == 16 || NM == 32, "J's rows live in registers, NM per lane");
+  extern __shared__ double lds[];
+  if (static_cast<int64_t>(blockIdx.x) >= A.S) return;
+  QpScene<ROWS_LDS, NM, 1> cx(A, lds);
+  cx.setup();
+  const QpLayout &lay = cx.lay;
+  const Rows &rw = cx.rw;
+  const ccmpc_mpc_params &p = A.p;
+  const int64_t mrows = cx.mrows;
+  const int lane = cx.lane, T = cx.T, n = cx.n, T3 = cx.T3, ldm = cx.ldm, order = cx.order;
+  double *Gs = cx.Gs, *M = cx.M, *Hc = cx.Hc, *y = cx.y, *z = cx.z, *bw = cx.bw, *red = cx.red;
+  const double tol_p = cx.tol_p;
+  int status = 0, it = 0;
+#ifdef CCMPC_QP_TRACE
+  const uint64_t tk1 = wall_clock64();
+#endif
+  // The strictly convex QP  min 1/2 z^T H z + f^T z  s.t.  g_r(z) <= 0  from its unconstrained
+  // minimum: the most violated row (normalised by its gradient's norm) enters the active set,
+  // primal steps along J2 d2 and dual steps along R^{-1} d1 keep the active multipliers >= 0
+  // (dropping a row whose multiplier reaches 0), until no row is violated beyond tol_p (an
+  // exact KKT point: the active rows hold as equalities, every multiplier >= 0) or no step
+  // exists (the rows are infeasible: CCMPC_QP_MAXITER, the reference's solve failure).  H =
+  // L L^T, J = L^{-T} rotated so that J^T N_A = [R; 0] (Givens rotations as rows enter and
+  // leave).  J lives in M's storage (row-major, stride ldm), R in the polish's S (row-major,
+  // upper triangle), the active rows and multipliers in the polish's act / dinv slots, the
+  // row norms and active flags in the IPM's row arrays is / dl.  A solve that exceeds its step
+  // budget or meets a non-finite value hands the scene to the IPM (returns false: the status
+  // becomes kQpNeedIpm, and the IPM pass launched next starts from its own setup).  The host
+  // launches this kernel only with the polish's blocks in the layout.
+  // Each active-set change is a handful of wave-wide LDS phases, and a T = 8 frame enters only
+  // a few rows, where the IPM spends ~5 iterations and a polish (~130 us).
+  auto gi_solve = [&]() -> bool {
+#ifdef CCMPC_QP_TRACE
+    uint64_t gmark[6] = {}, gacc[6] = {}, gt = 0;
+#define GI_MARK(i) (gmark[i] = wall_clock64())
+#define GI_T0() (gt = wall_clock64())
+#define GI_ACC(k)                         \
+  do {                                    \
+    const uint64_t gn_ = wall_clock64();  \
+    gacc[k] += gn_ - gt;                  \
+    gt = gn_;                             \
+  } while (0)
+#else
+#define GI_MARK(i) ((void)0)
+#define GI_T0() ((void)0)
+#define GI_ACC(k) ((void)0)
+#endif
+    GI_MARK(0);
+    double *Jm = M, *Rm = lds + lay.ps, *actv = lds + lay.pact, *uact = lds + lay.pdinv;
+    const double *fu = lds + lay.f;
+    double *inorm = rw.is, *aflag = rw.dl;
+    const int li = lane < n ? lane : 0;
+    auto gcol = [&](int i, int j) -> double {  // d v[i] / d z_j
+      return i < T3 ? Gs[i * n + j] : (i - T3 == j ? 1.0 : 0.0);
+    };
+    auto update_y = [&]() {  // y = Gs z (the output rows' linear part)
+      wave_sync();
+      if (lane < T3) {
+        double v = 0.0;
+#pragma unroll
+        for (int j = 0; j < NM; ++j)
+          if (j < n) v = fma(Gs[lane * n + j], z[j], v);
+        y[lane] = v;
+      }
+      wave_sync();
+    };
+    // H (no barrier terms) into M's lower triangle, as the polish builds it (n <= 32: entry by
+    // entry, as the four-wave polish does)
+    qp_build_hessian<1, NM>(M, Gs, Hc, n, ldm, T, order, p);
+    wave_sync();
+    double La[NM], Ldl = 0.0;
+    reg_load_lower(M, ldm, n, La);
+    if (reg_cholesky<NM, false>(La, Ldl)) return false;
+    GI_MARK(1);
+    // L (rows) and 1 / L_ii into R's storage (free until the first row enters) for the
+    // column-parallel inverse below
+    double *Ls = Rm, *Ldi = lds + lay.dinv;
+    reg_store_lower(Ls, ldm, n, La);
+    if (lane < n) Ldi[lane] = Ldl;
+    wave_sync();  // (every read of H is done too: J overwrites it)
+    GI_MARK(2);
+    // J = L^{-T}: lane c solves L x = e_c (all columns at once, L's entries broadcast from
+    // LDS), x_k = L^{-1}[k][c] = J[c][k] -- lane c ends with row c of J
+    double Jrow[NM];
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      double acc = (k == lane) ? 1.0 : 0.0;
+#pragma unroll
+      for (int j = 0; j < k; ++j)
+        if (k < n) acc = fma(-Ls[k * ldm + j], Jrow[j], acc);
+      Jrow[k] = k < n ? acc * Ldi[k < n ? k : 0] : 0.0;
+    }
+    if (lane < n) {
+#pragma unroll
+      for (int k = 0; k < NM; ++k)
+        if (k < n) Jm[lane * ldm + k] = Jrow[k];
+    }
+    // row gradient norms (the violation's scale) from each step's output-row Gram: an
+    // obstacle row's gradient is a0 Gs_x(t) + a1 Gs_y(t), a speed row's +-Gs_v(t), a box
+    // row's +-e_j
+    double *Ngr = bw;  // (the IPM's per-step weights: recomputed in its I1)
+    if (lane < T) {
+      double xx = 0.0, xy = 0.0, yy = 0.0, vv = 0.0;
+#pragma unroll
+      for (int j = 0; j < NM; ++j) {
+        if (j >= n) continue;
+        const double gx = Gs[(3 * lane) * n + j], gy = Gs[(3 * lane + 1) * n + j],
+                     gv = Gs[(3 * lane + 2) * n + j];
+        xx = fma(gx, gx, xx);
+        xy = fma(gx, gy, xy);
+        yy = fma(gy, gy, yy);
+        vv = fma(gv, gv, vv);
+      }
+      Ngr[4 * lane] = xx;
+      Ngr[4 * lane + 1] = xy;
+      Ngr[4 * lane + 2] = yy;
+      Ngr[4 * lane + 3] = vv;
+    }
+    wave_sync();
+    for (int64_t r = lane; r < mrows; r += 64) {
+      const int2 ix = reinterpret_cast<const int2 *>(rw.ix)[r];
+      const double a0 = rw.c0[r], a1 = rw.c1[r];
+      double s2;
+      if (ix.x >= T3) {
+        s2 = a0 * a0 + a1 * a1;                        // a box row (i0 == i1)
+      } else {
+        const int t = ix.x / 3;
+        s2 = (ix.x % 3 == 2) ? (a0 + a1) * (a0 + a1) * Ngr[4 * t + 3]
+                             : a0 * a0 * Ngr[4 * t] + 2.0 * a0 * a1 * Ngr[4 * t + 1] +
+                                   a1 * a1 * Ngr[4 * t + 2];
+      }
+      inorm[r] = s2 > 0.0 ? 1.0 / sqrt(s2) : 0.0;
+      aflag[r] = 0.0;
+    }
+    GI_MARK(3);
+    // the unconstrained minimum z = -J L^{-1} f (the forward solve on lane = row, then each
+    // lane's row of J against it)
+    {
+      const double y0 = reg_forward<NM>(La, Ldl, lane < n ? fu[lane] : 0.0);
+      double zi = 0.0;
+#pragma unroll
+      for (int k = 0; k < NM; ++k)
+        if (k < n) zi = fma(Jrow[k], lane_bcast(y0, k), zi);
+      wave_sync();
+      if (lane < n) z[lane] = -zi;
+    }
+    update_y();
+    GI_MARK(4);
+    int q = 0, steps = 0;
+    const int max_steps = A.gi_max_steps >= 0 ? A.gi_max_steps : 8 * (n + 16);
+    double *Rdi = lds + lay.dinv;  // 1 / R[k][k] (L's reciprocals are no longer needed)
+    // J stays in registers (lane i: row i, every rotation local); its LDS mirror serves the
+    // column reads of d = J^T m
+    auto store_j = [&]() {
+      if (lane < n) {
+#pragma unroll
+        for (int k = 0; k < NM; ++k)
+          if (k < n) Jm[lane * ldm + k] = Jrow[k];
+      }
+    };
+    // a Givens rotation zeroing b against a: c = a / h, s = b / h, h = |(a, b)|, from the
+    // hardware rsqrt with one Newton step (the rotation chain is serial; IEEE sqrt and two
+    // divisions per rotation were most of an active-set change)
+    auto givens = [](double a, double b, double &c, double &s, double &h) {
+      const double n2 = fma(a, a, b * b);
+      if (!(n2 > 0.0)) {
+        c = 1.0;
+        s = 0.0;
+        h = 0.0;
+        return;
+      }
+      double y = __builtin_amdgcn_rsq(n2);
+      y = y * fma(-0.5 * n2 * y, y, 1.5);
+      c = a * y;
+      s = b * y;
+      h = n2 * y;
+    };
+    while (true) {
+      GI_T0();
+      // the most violated row (normalised by its gradient), inactive rows only
+      double best = 0.0, bidx = -1.0, cviol = 0.0;
+#pragma unroll 2
+      for (int64_t r = lane; r < mrows; r += 64) {
+        const int2 ix = reinterpret_cast<const int2 *>(rw.ix)[r];
+        const double g = cx.row_g(r, y, z);
+        const double inr = inorm[r];
+        const bool on = aflag[r] == 0.0 && g > tol_p;
+        if (!isfinite(g)) cviol = 2.0;
+        if (on && inr == 0.0) cviol = fmax(cviol, 1.0);  // a violated constant row
+        const double v = g * inr;
+        if (on && v > best) {
+          best = v;
+          bidx = static_cast<double>(r);
+        }
+        (void)ix;
+      }
+      block_argmax<1>(best, bidx, red);
+      const double cv = wave_max(cviol);
+      GI_ACC(0);
+      if (cv >= 2.0) return false;
+      if (cv > 0.0) {  // no point satisfies it: infeasible
+        status = CCMPC_QP_MAXITER;
+        it = steps;
+        return true;
+      }
+      if (bidx < 0.0) break;  // every row holds: optimal
+      const int64_t pr = static_cast<int64_t>(bidx);
+      const int2 pix = reinterpret_cast<const int2 *>(rw.ix)[pr];
+      const double pc0 = rw.c0[pr], pc1 = rw.c1[pr];
+      // the entering row as m . z >= beta (m = -grad g): m_j on lane j
+      const double mj = lane < n ? -(pc0 * gcol(pix.x, li) + pc1 * gcol(pix.y, li)) : 0.0;
+      double sp = -cx.row_g(pr, y, z);  // its slack (< 0)
+      double uplus = 0.0;
+      // m, fixed while this row enters: broadcast through LDS (the IPM's rh slots, free
+      // here), read as VGPR operands -- sixteen readlane results held in SGPRs were part of
+      // the kernel's SGPR spilling
+      double *mvec = lds + lay.rh, *dvec = lds + lay.e2;
+      wave_sync();
+      if (lane < n) mvec[lane] = mj;
+      wave_sync();
+      while (true) {
+        if (++steps > max_steps) return false;
+        // d = J^T m (lane j), r = R^{-1} d[:q] (lane k < q)
+        double dj = 0.0;
+#pragma unroll
+        for (int i = 0; i < NM; ++i)
+          if (i < n) dj = fma(Jm[i * ldm + li], mvec[i], dj);
+        // back substitution with this lane's row of R and 1 / R_jj read from LDS up front
+        // (independent loads), the chain unrolled over j: a broadcast and an FMA per column
+        // instead of a dependent LDS round trip (the same operations, the same bits)
+        double rhs = dj, rk = 0.0;
+        double Rrow[NM];
+#pragma unroll
+        for (int k = 0; k < NM; ++k) Rrow[k] = Rm[li * ldm + k];  // (k >= n: see QpLayout)
+        const double rdl = Rdi[li];
+#pragma unroll
+        for (int j = NM - 1; j >= 0; --j) {
+          if (j >= q) continue;  // uniform
+          const double xj = lane_bcast(rhs, j) * lane_bcast(rdl, j);
+          if (lane == j) rk = xj;
+          if (lane < j) rhs = fma(-Rrow[j], xj, rhs);
+        }
+        GI_ACC(1);
+        double dd[NM];
+        wave_sync();
+        if (lane < n) dvec[lane] = dj;
+        wave_sync();
+#pragma unroll
+        for (int k = 0; k < NM; ++k) dd[k] = dvec[k < n ? k : 0];
+        double d2 = 0.0, dn2 = 0.0, zi = 0.0;
+#pragma unroll
+        for (int k = 0; k < NM; ++k) {
+          if (k >= n) continue;
+          dn2 = fma(dd[k], dd[k], dn2);
+          if (k >= q) {
+            d2 = fma(dd[k], dd[k], d2);
+            zi = fma(Jrow[k], dd[k], zi);  // J2 d2: the primal direction
+          }
+        }
+        if (!isfinite(dn2)) return false;
+        const bool zero_step = !(d2 > 1e-24 * dn2);
+        // partial step: the first active multiplier to reach 0 (smallest lane on ties)
+        const double ratio =
+            (lane < q && rk > 0.0) ? uact[lane < q ? lane : 0] / rk : INFINITY;
+        const double t1 = wave_min(ratio);
+        const int l =
+            t1 < INFINITY
+                ? __ffsll(static_cast<long long>(__ballot(lane < q && ratio == t1))) - 1
+                : -1;
+        const double t2 = zero_step ? INFINITY : -sp / d2;
+        // no step exists: the entering row's normal lies in the span of the active normals
+        // (d2 ~ 0) with coefficients r <= 0, and the row is violated at a point where every
+        // active row holds -- a Farkas certificate that the rows are infeasible (the
+        // reference's solve failure): any z meeting the active rows has m.z <= sum_j r_j
+        // beta_j = beta + sp < beta.  Its tests compare against round-off scales (zero_step,
+        // rk > 0), which near-parallel rows of several cells at one t can tip;
+        // an entry r_j ~ 0 of the wrong sign moves m.z by |r_j| |n_j . z| only, so the
+        // verdict is kept when the entering row's violation is far above that scale (1e-6 of
+        // its gradient's norm), and a marginal one is handed to the IPM, which confirms it
+        // or finds the point
+        if (!(t1 < INFINITY) && !(t2 < INFINITY)) {
+          const double viol = -sp * inorm[pr];
+          const bool certain = viol > 1e-6;
+          if (A.gi_nostep == 1 || (A.gi_nostep == 2 && !certain)) return false;
+          status = CCMPC_QP_MAXITER;
+          it = steps;
+          return true;
+        }
+        GI_ACC(2);
+        const double t = fmin(t1, t2);
+        wave_sync();
+        if (lane < q) uact[lane] -= t * rk;
+        if (!zero_step && lane < n) z[lane] += t * zi;
+        uplus += t;
+        if (!zero_step) sp = fma(t, d2, sp);
+        const bool full = !zero_step && t2 <= t1;
+        if (full) {
+          // add the row: rotate d[q:] onto d[q] (J's columns q .. n-1), R's new column
+          double (&dv)[NM] = dd;  // rotated in place (dd is not read again)
+#pragma unroll
+          for (int j = NM - 1; j >= 1; --j) {
+            if (j >= n || j <= q) continue;
+            double c, s, h;
+            givens(dv[j - 1], dv[j], c, s, h);
+            dv[j - 1] = h;
+            dv[j] = 0.0;
+            const double x0 = Jrow[j - 1], x1 = Jrow[j];
+            Jrow[j - 1] = fma(c, x0, s * x1);
+            Jrow[j] = fma(-s, x0, c * x1);
+          }
+          double rqq = 0.0;
+#pragma unroll
+          for (int k = 0; k < NM; ++k)
+            if (k == q) rqq = dv[k];
+          if (rqq < 0.0) {
+            rqq = -rqq;
+#pragma unroll
+            for (int k = 0; k < NM; ++k)
+              if (k == q) Jrow[k] = -Jrow[k];
+          }
+          if (!(rqq > 1e-300)) return false;  // dependent row with a primal step
+          wave_sync();
+          store_j();
+          if (lane < q) Rm[lane * ldm + q] = dj;
+          if (lane == q) {
+            Rm[q * ldm + q] = rqq;
+            Rdi[q] = 1.0 / rqq;
+            actv[q] = static_cast<double>(pr);
+            uact[q] = uplus;
+          }
+          if (lane == 0) aflag[pr] = 1.0;
+          ++q;
+          GI_ACC(3);
+          update_y();
+          GI_ACC(5);
+          break;
+        }
+        // drop active row l: R's columns l+1 .. q-1 shift left (lane = column), then
+        // rotations on rows (k, k+1), k = l .. q-2, restore the triangle; J's columns
+        // (k, k+1) likewise
+        double Rc[NM];
+        {
+          const int col = (lane >= l && lane < q - 1) ? lane + 1 : (lane < q ? lane : 0);
+#pragma unroll
+          for (int i = 0; i < NM; ++i) Rc[i] = (i < q) ? Rm[i * ldm + col] : 0.0;
+        }
+        // (k unrolled: registers indexed directly, no select over the whole row per rotation)
+#pragma unroll
+        for (int k = 0; k < NM - 1; ++k) {
+          if (k < l || k >= q - 1) continue;  // uniform
+          double c, s, h;
+          givens(lane_bcast(Rc[k], k), lane_bcast(Rc[k + 1], k), c, s, h);
+          const double r0 = Rc[k], r1 = Rc[k + 1];
+          Rc[k] = fma(c, r0, s * r1);
+          Rc[k + 1] = fma(-s, r0, c * r1);
+          const double x0 = Jrow[k], x1 = Jrow[k + 1];
+          Jrow[k] = fma(c, x0, s * x1);
+          Jrow[k + 1] = fma(-s, x0, c * x1);
+        }
+        double rdg = 1.0;
+#pragma unroll
+        for (int i = 0; i < NM; ++i)
+          if (i == lane) rdg = Rc[i];
+        const double act_next = actv[(lane + 1 < q ? lane + 1 : 0)];
+        const double u_next = uact[(lane + 1 < q ? lane + 1 : 0)];
+        const double dropped = actv[l];
+        wave_sync();
+        if (lane < q - 1) {
+#pragma unroll
+          for (int i = 0; i < NM; ++i)
+            if (i <= lane) Rm[i * ldm + lane] = Rc[i];
+          Rdi[lane] = 1.0 / rdg;
+          if (lane >= l) {
+            actv[lane] = act_next;
+            uact[lane] = u_next;
+          }
+        }
+        store_j();
+        if (lane == 0) aflag[static_cast<int64_t>(dropped)] = 0.0;
+        --q;
+        GI_ACC(4);
+        update_y();
+        GI_ACC(5);
+        if (!zero_step) sp = -cx.row_g(pr, y, z);  // the entering row's slack at the new point
+      }
+    }
+    status = 0;
+    it = steps;
+#ifdef CCMPC_QP_TRACE
+    GI_MARK(5);
+    if (lane == 0 && cx.sc == 0)
+      printf("gi phases (10ns): H+chol %d L %d J+norms %d z0 %d loop %d (steps %d, q %d)\n"
+             "   loop: scan %d d+r %d dir+ratios %d add %d drop %d update_y %d\n",
+             int(gmark[1] - gmark[0]), int(gmark[2] - gmark[1]), int(gmark[3] - gmark[2]),
+             int(gmark[4] - gmark[3]), int(gmark[5] - gmark[4]), steps, q, int(gacc[0]),
+             int(gacc[1]), int(gacc[2]), int(gacc[3]), int(gacc[4]), int(gacc[5]));
+#endif
+#undef GI_MARK
+#undef GI_T0
+#undef GI_ACC
+    return true;
+  };
+  if (!gi_solve()) status = kQpNeedIpm;  // the IPM pass launched next takes this scene
+#ifdef CCMPC_QP_TRACE
+  const uint64_t tk2 = wall_clock64();
+#endif
+  cx.output(status, it);
+#ifdef CCMPC_QP_TRACE
+  if (lane == 0 && cx.sc == 0)
+    printf("qp setup (10ns): model %d rows %d f %d init %d\n"
+           "qp phases (10ns): setup %d active set %d outputs %d\n",
+           int(cx.smark[0] - cx.tk0), int(cx.smark[1] - cx.smark[0]),
+           int(cx.smark[2] - cx.smark[1]), int(cx.smark[3] - cx.smark[2]), int(tk1 - cx.tk0),
+           int(tk2 - tk1), int(wall_clock64() - tk2));
+#endif
+}
+
+// ---- the interior point method and its polish ------------------------------------------------
+// Launched alone (CCMPC_QP_METHOD_IPM, n > 32, or no room for the polish's blocks), or as the
+// pass after mpc_qp_gi_kernel with A.fallback_only, for the scenes that one handed over.
+template <bool ROWS_LDS, int NM, int NW>
+__global__ __launch_bounds__(64 * NW) void mpc_qp_ipm_kernel(QpArgs A) {
+#pragma clang fp contract(fast)  // see QpScene
+  constexpr int NTH = 64 * NW;
+  extern __shared__ double lds[];
+  if (static_cast<int64_t>(blockIdx.x) >= A.S) return;
+  if (A.fallback_only && !(A.out_status[blockIdx.x] & kQpNeedIpm)) return;
+  QpScene<ROWS_LDS, NM, NW> cx(A, lds);
+  cx.setup();
+  const QpLayout &lay = cx.lay;
+  const Rows &rw = cx.rw;
+  const ccmpc_mpc_params &p = A.p;
+  const int64_t ncell = cx.ncell, mrows = cx.mrows;
+  const int tid = cx.tid, lane = cx.lane, w = cx.w, T = cx.T, P = cx.P, n = cx.n, T3 = cx.T3,
+            ldm = cx.ldm, nbox = cx.nbox, nv = cx.nv, order = cx.order;
+  double *Gs = cx.Gs, *M = cx.M, *Hc = cx.Hc, *y = cx.y, *yd = cx.yd, *qf = cx.qf, *q = cx.q,
+         *bw = cx.bw, *z = cx.z, *dz = cx.dz, *rd = cx.rd, *rh = cx.rh, *e2 = cx.e2,
+         *dinv = cx.dinv, *red = cx.red;
+  const double *oa0 = cx.oa0, *oa1 = cx.oa1;
+  const double tol_p = cx.tol_p, tol_d = cx.tol_d;
 
   // Per-step sums over a step's obstacle rows, in a fixed order (wave per step, lane-strided,
   // butterfly reduction).  Step t's rows of cell c are the run [start_t, start_t + cnt_t) of
@@ -973,42 +1206,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     double *fu = lds + lay.f, *y0 = rh, *rs = e2, *lam = q, *zp = dz, *yp = yd;
     PQ_MARK(0);
     // H (no barrier terms) into M; f in control space (fu) is the setup's
-    if constexpr (NW == 1 && NM == 16) {  // as the IPM's M: lane column jm, rows (lane >> 4) + 4 m
-      const int jm = lane & 15, jc = jm < n ? jm : 0;
-      double hx[8], hy[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int tt = t < T ? t : 0;
-        const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
-        hx[t] = t < T ? wp * Gs[(3 * tt) * n + jc] : 0.0;
-        hy[t] = t < T ? wp * Gs[(3 * tt + 1) * n + jc] : 0.0;
-      }
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int im = (lane >> 4) + 4 * m;
-        const bool on = im < n && jm <= im;
-        const int ic = on ? im : 0;
-        double v = Hc[ic * n + jc];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          const int tt = t < T ? t : 0;
-          v = fma(Gs[(3 * tt) * n + ic], hx[t], fma(Gs[(3 * tt + 1) * n + ic], hy[t], v));
-        }
-        if (on) M[im * ldm + jm] = v;
-      }
-    } else {
-      for (int e = tid; e < n * n; e += NTH) {
-        const int i = e / n, j = e % n;
-        if (j > i) continue;
-        double v = hctrl(i, j, T, order, p);
-        for (int t = 0; t < T; ++t) {
-          const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
-          v += wp * (Gs[(3 * t) * n + i] * Gs[(3 * t) * n + j] +
-                     Gs[(3 * t + 1) * n + i] * Gs[(3 * t + 1) * n + j]);
-        }
-        M[i * ldm + j] = v;
-      }
-    }
+    qp_build_hessian<NW, NM>(M, Gs, Hc, n, ldm, T, order, p);
     PQ_MARK(1);
     // active rows, compacted in row order (ballot + prefix: deterministic)
     int na = 0;
@@ -1027,21 +1225,15 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
       na = tot;
       qp_sync<NW>();
     }
-    if constexpr (NM > 0 && NW == 1) {
+    if constexpr (NM > 0) {
       PQ_MARK(2);
       // One wave, n <= 16: the same polish with every factor in registers (identity-padded
       // to 16 x 16, straight-line; reg_cholesky without the pivot skip), the L^T columns read
       // ahead of each backward chain, the vectors moved between lanes by readlane.
       wave_sync();
-#pragma unroll
-      for (int k = 0; k < NR; ++k) {
-        const double v = M[(lane < n ? lane : 0) * ldm + (k < n ? k : 0)];
-        La[k] = (lane < n && k <= lane) ? v : (k == lane ? 1.0 : 0.0);
-      }
+      reg_load_lower(M, ldm, n, La);
       const bool hfail = reg_cholesky<NR, false>(La, Ldl);
-#pragma unroll
-      for (int k = 0; k < NR; ++k)
-        if (k < n && lane < n && k <= lane) M[lane * ldm + k] = La[k];
+      reg_store_lower(M, ldm, n, La);
       wave_sync();
       double ltH[NR];
       reg_load_lt(M, ldm, n, ltH);
@@ -1079,7 +1271,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
 #pragma unroll
             for (int j = 0; j < NR; ++j)
               if (j < n) Wm[lane * n + j] = wv[j];
-            rs[lane] = d + row_const(r);
+            rs[lane] = d + cx.row_const(r);
           }
         }
         wave_sync();
@@ -1102,16 +1294,10 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
         }
         wave_sync();
         double Ls[NR], Sdl = 0.0;
-#pragma unroll
-        for (int k = 0; k < NR; ++k) {
-          const double v = Sm[(lane < na ? lane : 0) * ldm + (k < na ? k : 0)];
-          Ls[k] = (lane < na && k <= lane) ? v : (k == lane ? 1.0 : 0.0);
-        }
+        reg_load_lower(Sm, ldm, na, Ls);
         const bool sfail = reg_cholesky<NR, false>(Ls, Sdl);
         if (sfail) break;  // dependent active rows
-#pragma unroll
-        for (int k = 0; k < NR; ++k)
-          if (k < na && lane < na && k <= lane) Sm[lane * ldm + k] = Ls[k];
+        reg_store_lower(Sm, ldm, na, Ls);
         wave_sync();
         const double lamr = reg_solve(Ls, Sm, ldm, Sdl, na, lane < na ? rs[lane] : 0.0);
         if (lane < na) lam[lane] = lamr;
@@ -1141,7 +1327,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
         PQ_MARK(6);
         double viol = -1e300, vrow = 0.0, lneg = 0.0, bad = 0.0;
         for (int64_t r = tid; r < mrows; r += NTH) {
-          const double g = row_g(r, yp, zp);
+          const double g = cx.row_g(r, yp, zp);
           if (!isfinite(g)) bad = 1.0;
           if (g > viol) {
             viol = g;
@@ -1227,7 +1413,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
           for (int h = 0; h < 2; ++h)
             if (lane + 64 * h < n) d += b[h] * y0[lane + 64 * h];
           d = wave_sum(d);
-          if (lane == 0) rs[a] = d + row_const(r);
+          if (lane == 0) rs[a] = d + cx.row_const(r);
         }
         qp_sync<NW>();
         for (int e = tid; e < na * na; e += NTH) {
@@ -1273,7 +1459,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
         qp_sync<NW>();
         double viol = -1e300, vrow = 0.0, lneg = 0.0, bad = 0.0;
         for (int64_t r = tid; r < mrows; r += NTH) {
-          const double g = row_g(r, yp, zp);
+          const double g = cx.row_g(r, yp, zp);
           if (!isfinite(g)) bad = 1.0;
           if (g > viol) {
             viol = g;
@@ -1319,7 +1505,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
   // M = H_ctrl + D_box + sum_t Gs_t^T B_t Gs_t (the barrier-weighted normal matrix of I2).
   // A lambda so a failed early polish, which factors H in M's storage, can rebuild it.
   auto normal_matrix = [&]() {
-    if constexpr (NW == 1 && NM == 16) {
+    if constexpr (NM == 16) {
       // lane column jm = lane & 15 (its weighted Gs columns in registers), rows
       // im = (lane >> 4) + 4 m
       const int jm = lane & 15, jc = jm < n ? jm : 0;
@@ -1370,464 +1556,14 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     }
   };
 
-  // ---- Goldfarb-Idnani dual active-set solve (one wave, n <= 32; CCMPC_QP_METHOD_GI) --------
-  // The strictly convex QP  min 1/2 z^T H z + f^T z  s.t.  g_r(z) <= 0  from its unconstrained
-  // minimum: the most violated row (normalised by its gradient's norm) enters the active set,
-  // primal steps along J2 d2 and dual steps along R^{-1} d1 keep the active multipliers >= 0
-  // (dropping a row whose multiplier reaches 0), until no row is violated beyond tol_p (an
-  // exact KKT point: the active rows hold as equalities, every multiplier >= 0) or no step
-  // exists (the rows are infeasible: CCMPC_QP_MAXITER, the reference's solve failure).  H =
-  // L L^T, J = L^{-T} rotated so that J^T N_A = [R; 0] (Givens rotations as rows enter and
-  // leave).  J lives in M's storage (row-major, stride ldm), R in the polish's S (row-major,
-  // upper triangle), the active rows and multipliers in the polish's act / dinv slots, the
-  // row norms and active flags in the IPM's row arrays is / dl.  A solve that exceeds its step
-  // budget or meets a non-finite value hands the problem to the IPM (returns false, z = y = 0).
-  // Each active-set change is a handful of wave-wide LDS phases, and a T = 8 frame enters only
-  // a few rows, where the IPM spends ~5 iterations and a polish (~130 us).
-  bool gi_done = false;
-  if constexpr (GI && NW == 1 && (NM == 16 || NM == 32)) {
-    auto gi_solve = [&]() -> bool {
-#ifdef CCMPC_QP_TRACE
-      uint64_t gmark[6] = {}, gacc[6] = {}, gt = 0;
-#define GI_MARK(i) (gmark[i] = wall_clock64())
-#define GI_T0() (gt = wall_clock64())
-#define GI_ACC(k)                         \
-  do {                                    \
-    const uint64_t gn_ = wall_clock64();  \
-    gacc[k] += gn_ - gt;                  \
-    gt = gn_;                             \
-  } while (0)
-#else
-#define GI_MARK(i) ((void)0)
-#define GI_T0() ((void)0)
-#define GI_ACC(k) ((void)0)
-#endif
-      GI_MARK(0);
-      double *Jm = M, *Rm = lds + lay.ps, *actv = lds + lay.pact, *uact = lds + lay.pdinv;
-      const double *fu = lds + lay.f;
-      double *inorm = rw.is, *aflag = rw.dl;
-      const int li = lane < n ? lane : 0;
-      auto gcol = [&](int i, int j) -> double {  // d v[i] / d z_j
-        return i < T3 ? Gs[i * n + j] : (i - T3 == j ? 1.0 : 0.0);
-      };
-      auto update_y = [&]() {  // y = Gs z (the output rows' linear part)
-        wave_sync();
-        if (lane < T3) {
-          double v = 0.0;
-  #pragma unroll
-          for (int j = 0; j < NM; ++j)
-            if (j < n) v = fma(Gs[lane * n + j], z[j], v);
-          y[lane] = v;
-        }
-        wave_sync();
-      };
-      auto give_up = [&]() -> bool {  // back to the IPM's starting point
-        wave_sync();
-        if (lane < n) z[lane] = 0.0;
-        if (lane < T3) y[lane] = 0.0;
-        for (int64_t r = lane; r < mrows; r += 64) rw.is[r] = 1.0 / rw.s[r];
-        wave_sync();
-        return false;
-      };
-      // H (no barrier terms) into M's lower triangle, as the polish builds it (n <= 32: entry by
-      // entry, as the four-wave polish does)
-      if constexpr (NM == 32) {
-        for (int e = lane; e < n * n; e += 64) {
-          const int i = e / n, j = e % n;
-          if (j > i) continue;
-          double v = hctrl(i, j, T, order, p);
-          for (int t = 0; t < T; ++t) {
-            const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
-            v += wp * (Gs[(3 * t) * n + i] * Gs[(3 * t) * n + j] +
-                       Gs[(3 * t + 1) * n + i] * Gs[(3 * t + 1) * n + j]);
-          }
-          M[i * ldm + j] = v;
-        }
-      } else {
-        const int jm = lane & 15, jc = jm < n ? jm : 0;
-        double hx[8], hy[8];
-  #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          const int tt = t < T ? t : 0;
-          const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
-          hx[t] = t < T ? wp * Gs[(3 * tt) * n + jc] : 0.0;
-          hy[t] = t < T ? wp * Gs[(3 * tt + 1) * n + jc] : 0.0;
-        }
-  #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const int im = (lane >> 4) + 4 * m;
-          const bool on = im < n && jm <= im;
-          const int ic = on ? im : 0;
-          double v = Hc[ic * n + jc];
-  #pragma unroll
-          for (int t = 0; t < 8; ++t) {
-            const int tt = t < T ? t : 0;
-            v = fma(Gs[(3 * tt) * n + ic], hx[t], fma(Gs[(3 * tt + 1) * n + ic], hy[t], v));
-          }
-          if (on) M[im * ldm + jm] = v;
-        }
-      }
-      wave_sync();
-      double La[NM], Ldl = 0.0;
-  #pragma unroll
-      for (int k = 0; k < NM; ++k) {
-        const double v = M[li * ldm + (k < n ? k : 0)];
-        La[k] = (lane < n && k <= lane) ? v : (k == lane ? 1.0 : 0.0);
-      }
-      if (reg_cholesky<NM, false>(La, Ldl)) return give_up();
-      GI_MARK(1);
-      // L (rows) and 1 / L_ii into R's storage (free until the first row enters) for the
-      // column-parallel inverse below
-      double *Ls = Rm, *Ldi = lds + lay.dinv;
-      if (lane < n) {
-#pragma unroll
-        for (int k = 0; k < NM; ++k)
-          if (k <= lane && k < n) Ls[lane * ldm + k] = La[k];
-        Ldi[lane] = Ldl;
-      }
-      wave_sync();  // (every read of H is done too: J overwrites it)
-      GI_MARK(2);
-      // J = L^{-T}: lane c solves L x = e_c (all columns at once, L's entries broadcast from
-      // LDS), x_k = L^{-1}[k][c] = J[c][k] -- lane c ends with row c of J
-      double Jrow[NM];
-#pragma unroll
-      for (int k = 0; k < NM; ++k) {
-        double acc = (k == lane) ? 1.0 : 0.0;
-#pragma unroll
-        for (int j = 0; j < k; ++j)
-          if (k < n) acc = fma(-Ls[k * ldm + j], Jrow[j], acc);
-        Jrow[k] = k < n ? acc * Ldi[k < n ? k : 0] : 0.0;
-      }
-      if (lane < n) {
-#pragma unroll
-        for (int k = 0; k < NM; ++k)
-          if (k < n) Jm[lane * ldm + k] = Jrow[k];
-      }
-      // row gradient norms (the violation's scale) from each step's output-row Gram: an
-      // obstacle row's gradient is a0 Gs_x(t) + a1 Gs_y(t), a speed row's +-Gs_v(t), a box
-      // row's +-e_j
-      double *Ngr = bw;  // (the IPM's per-step weights: recomputed in its I1)
-      if (lane < T) {
-        double xx = 0.0, xy = 0.0, yy = 0.0, vv = 0.0;
-#pragma unroll
-        for (int j = 0; j < NM; ++j) {
-          if (j >= n) continue;
-          const double gx = Gs[(3 * lane) * n + j], gy = Gs[(3 * lane + 1) * n + j],
-                       gv = Gs[(3 * lane + 2) * n + j];
-          xx = fma(gx, gx, xx);
-          xy = fma(gx, gy, xy);
-          yy = fma(gy, gy, yy);
-          vv = fma(gv, gv, vv);
-        }
-        Ngr[4 * lane] = xx;
-        Ngr[4 * lane + 1] = xy;
-        Ngr[4 * lane + 2] = yy;
-        Ngr[4 * lane + 3] = vv;
-      }
-      wave_sync();
-      for (int64_t r = lane; r < mrows; r += 64) {
-        const int2 ix = reinterpret_cast<const int2 *>(rw.ix)[r];
-        const double a0 = rw.c0[r], a1 = rw.c1[r];
-        double s2;
-        if (ix.x >= T3) {
-          s2 = a0 * a0 + a1 * a1;                        // a box row (i0 == i1)
-        } else {
-          const int t = ix.x / 3;
-          s2 = (ix.x % 3 == 2) ? (a0 + a1) * (a0 + a1) * Ngr[4 * t + 3]
-                               : a0 * a0 * Ngr[4 * t] + 2.0 * a0 * a1 * Ngr[4 * t + 1] +
-                                     a1 * a1 * Ngr[4 * t + 2];
-        }
-        inorm[r] = s2 > 0.0 ? 1.0 / sqrt(s2) : 0.0;
-        aflag[r] = 0.0;
-      }
-      GI_MARK(3);
-      // the unconstrained minimum z = -J L^{-1} f (the forward solve on lane = row, then each
-      // lane's row of J against it)
-      {
-        const double y0 = reg_forward<NM>(La, Ldl, lane < n ? fu[lane] : 0.0);
-        double zi = 0.0;
-#pragma unroll
-        for (int k = 0; k < NM; ++k)
-          if (k < n) zi = fma(Jrow[k], lane_bcast(y0, k), zi);
-        wave_sync();
-        if (lane < n) z[lane] = -zi;
-      }
-      update_y();
-      GI_MARK(4);
-      int q = 0, steps = 0;
-      const int max_steps = A.gi_max_steps >= 0 ? A.gi_max_steps : 8 * (n + 16);
-      double *Rdi = lds + lay.dinv;  // 1 / R[k][k] (L's reciprocals are no longer needed)
-      // J stays in registers (lane i: row i, every rotation local); its LDS mirror serves the
-      // column reads of d = J^T m
-      auto store_j = [&]() {
-        if (lane < n) {
-#pragma unroll
-          for (int k = 0; k < NM; ++k)
-            if (k < n) Jm[lane * ldm + k] = Jrow[k];
-        }
-      };
-      // a Givens rotation zeroing b against a: c = a / h, s = b / h, h = |(a, b)|, from the
-      // hardware rsqrt with one Newton step (the rotation chain is serial; IEEE sqrt and two
-      // divisions per rotation were most of an active-set change)
-      auto givens = [](double a, double b, double &c, double &s, double &h) {
-        const double n2 = fma(a, a, b * b);
-        if (!(n2 > 0.0)) {
-          c = 1.0;
-          s = 0.0;
-          h = 0.0;
-          return;
-        }
-        double y = __builtin_amdgcn_rsq(n2);
-        y = y * fma(-0.5 * n2 * y, y, 1.5);
-        c = a * y;
-        s = b * y;
-        h = n2 * y;
-      };
-      while (true) {
-        GI_T0();
-        // the most violated row (normalised by its gradient), inactive rows only
-        double best = 0.0, bidx = -1.0, cviol = 0.0;
-#pragma unroll 2
-        for (int64_t r = lane; r < mrows; r += 64) {
-          const int2 ix = reinterpret_cast<const int2 *>(rw.ix)[r];
-          const double g = row_g(r, y, z);
-          const double inr = inorm[r];
-          const bool on = aflag[r] == 0.0 && g > tol_p;
-          if (!isfinite(g)) cviol = 2.0;
-          if (on && inr == 0.0) cviol = fmax(cviol, 1.0);  // a violated constant row
-          const double v = g * inr;
-          if (on && v > best) {
-            best = v;
-            bidx = static_cast<double>(r);
-          }
-          (void)ix;
-        }
-        block_argmax<1>(best, bidx, red);
-        const double cv = wave_max(cviol);
-        GI_ACC(0);
-        if (cv >= 2.0) return give_up();
-        if (cv > 0.0) {  // no point satisfies it: infeasible
-          status = CCMPC_QP_MAXITER;
-          infeasible = true;
-          it = steps;
-          return true;
-        }
-        if (bidx < 0.0) break;  // every row holds: optimal
-        const int64_t pr = static_cast<int64_t>(bidx);
-        const int2 pix = reinterpret_cast<const int2 *>(rw.ix)[pr];
-        const double pc0 = rw.c0[pr], pc1 = rw.c1[pr];
-        // the entering row as m . z >= beta (m = -grad g): m_j on lane j
-        const double mj = lane < n ? -(pc0 * gcol(pix.x, li) + pc1 * gcol(pix.y, li)) : 0.0;
-        double sp = -row_g(pr, y, z);  // its slack (< 0)
-        double uplus = 0.0;
-        // m, fixed while this row enters: broadcast through LDS (the IPM's rh slots, free
-        // here), read as VGPR operands -- sixteen readlane results held in SGPRs were part of
-        // the kernel's SGPR spilling
-        double *mvec = lds + lay.rh, *dvec = lds + lay.e2;
-        wave_sync();
-        if (lane < n) mvec[lane] = mj;
-        wave_sync();
-        while (true) {
-          if (++steps > max_steps) return give_up();
-          // d = J^T m (lane j), r = R^{-1} d[:q] (lane k < q)
-          double dj = 0.0;
-#pragma unroll
-          for (int i = 0; i < NM; ++i)
-            if (i < n) dj = fma(Jm[i * ldm + li], mvec[i], dj);
-          // back substitution with this lane's row of R and 1 / R_jj read from LDS up front
-          // (independent loads), the chain unrolled over j: a broadcast and an FMA per column
-          // instead of a dependent LDS round trip (the same operations, the same bits)
-          double rhs = dj, rk = 0.0;
-          double Rrow[NM];
-#pragma unroll
-          for (int k = 0; k < NM; ++k) Rrow[k] = Rm[li * ldm + k];
-          const double rdl = Rdi[li];
-#pragma unroll
-          for (int j = NM - 1; j >= 0; --j) {
-            if (j >= q) continue;  // uniform
-            const double xj = lane_bcast(rhs, j) * lane_bcast(rdl, j);
-            if (lane == j) rk = xj;
-            if (lane < j) rhs = fma(-Rrow[j], xj, rhs);
-          }
-          GI_ACC(1);
-          double dd[NM];
-          wave_sync();
-          if (lane < n) dvec[lane] = dj;
-          wave_sync();
-#pragma unroll
-          for (int k = 0; k < NM; ++k) dd[k] = dvec[k < n ? k : 0];
-          double d2 = 0.0, dn2 = 0.0, zi = 0.0;
-#pragma unroll
-          for (int k = 0; k < NM; ++k) {
-            if (k >= n) continue;
-            dn2 = fma(dd[k], dd[k], dn2);
-            if (k >= q) {
-              d2 = fma(dd[k], dd[k], d2);
-              zi = fma(Jrow[k], dd[k], zi);  // J2 d2: the primal direction
-            }
-          }
-          if (!isfinite(dn2)) return give_up();
-          const bool zero_step = !(d2 > 1e-24 * dn2);
-          // partial step: the first active multiplier to reach 0 (smallest lane on ties)
-          const double ratio =
-              (lane < q && rk > 0.0) ? uact[lane < q ? lane : 0] / rk : INFINITY;
-          const double t1 = wave_min(ratio);
-          const int l =
-              t1 < INFINITY
-                  ? __ffsll(static_cast<long long>(__ballot(lane < q && ratio == t1))) - 1
-                  : -1;
-          const double t2 = zero_step ? INFINITY : -sp / d2;
-          // no step exists: the entering row's normal lies in the span of the active normals
-          // (d2 ~ 0) with coefficients r <= 0, and the row is violated at a point where every
-          // active row holds -- a Farkas certificate that the rows are infeasible (the
-          // reference's solve failure): any z meeting the active rows has m.z <= sum_j r_j
-          // beta_j = beta + sp < beta.  Its tests compare against round-off scales (zero_step,
-          // rk > 0), which near-parallel rows of several cells at one t can tip;
-          // an entry r_j ~ 0 of the wrong sign moves m.z by |r_j| |n_j . z| only, so the
-          // verdict is kept when the entering row's violation is far above that scale (1e-6 of
-          // its gradient's norm), and a marginal one is handed to the IPM, which confirms it
-          // or finds the point
-          if (!(t1 < INFINITY) && !(t2 < INFINITY)) {
-            const double viol = -sp * inorm[pr];
-            const bool certain = viol > 1e-6;
-            if (A.gi_nostep == 1 || (A.gi_nostep == 2 && !certain)) return give_up();
-            status = CCMPC_QP_MAXITER;
-            infeasible = true;
-            it = steps;
-            return true;
-          }
-          GI_ACC(2);
-          const double t = fmin(t1, t2);
-          wave_sync();
-          if (lane < q) uact[lane] -= t * rk;
-          if (!zero_step && lane < n) z[lane] += t * zi;
-          uplus += t;
-          if (!zero_step) sp = fma(t, d2, sp);
-          const bool full = !zero_step && t2 <= t1;
-          if (full) {
-            // add the row: rotate d[q:] onto d[q] (J's columns q .. n-1), R's new column
-            double (&dv)[NM] = dd;  // rotated in place (dd is not read again)
-#pragma unroll
-            for (int j = NM - 1; j >= 1; --j) {
-              if (j >= n || j <= q) continue;
-              double c, s, h;
-              givens(dv[j - 1], dv[j], c, s, h);
-              dv[j - 1] = h;
-              dv[j] = 0.0;
-              const double x0 = Jrow[j - 1], x1 = Jrow[j];
-              Jrow[j - 1] = fma(c, x0, s * x1);
-              Jrow[j] = fma(-s, x0, c * x1);
-            }
-            double rqq = 0.0;
-#pragma unroll
-            for (int k = 0; k < NM; ++k)
-              if (k == q) rqq = dv[k];
-            if (rqq < 0.0) {
-              rqq = -rqq;
-#pragma unroll
-              for (int k = 0; k < NM; ++k)
-                if (k == q) Jrow[k] = -Jrow[k];
-            }
-            if (!(rqq > 1e-300)) return give_up();  // dependent row with a primal step
-            wave_sync();
-            store_j();
-            if (lane < q) Rm[lane * ldm + q] = dj;
-            if (lane == q) {
-              Rm[q * ldm + q] = rqq;
-              Rdi[q] = 1.0 / rqq;
-              actv[q] = static_cast<double>(pr);
-              uact[q] = uplus;
-            }
-            if (lane == 0) aflag[pr] = 1.0;
-            ++q;
-            GI_ACC(3);
-            update_y();
-            GI_ACC(5);
-            break;
-          }
-          // drop active row l: R's columns l+1 .. q-1 shift left (lane = column), then
-          // rotations on rows (k, k+1), k = l .. q-2, restore the triangle; J's columns
-          // (k, k+1) likewise
-          double Rc[NM];
-          {
-            const int col = (lane >= l && lane < q - 1) ? lane + 1 : (lane < q ? lane : 0);
-#pragma unroll
-            for (int i = 0; i < NM; ++i) Rc[i] = (i < q) ? Rm[i * ldm + col] : 0.0;
-          }
-          // (k unrolled: registers indexed directly, no select over the whole row per rotation)
-#pragma unroll
-          for (int k = 0; k < NM - 1; ++k) {
-            if (k < l || k >= q - 1) continue;  // uniform
-            double c, s, h;
-            givens(lane_bcast(Rc[k], k), lane_bcast(Rc[k + 1], k), c, s, h);
-            const double r0 = Rc[k], r1 = Rc[k + 1];
-            Rc[k] = fma(c, r0, s * r1);
-            Rc[k + 1] = fma(-s, r0, c * r1);
-            const double x0 = Jrow[k], x1 = Jrow[k + 1];
-            Jrow[k] = fma(c, x0, s * x1);
-            Jrow[k + 1] = fma(-s, x0, c * x1);
-          }
-          double rdg = 1.0;
-#pragma unroll
-          for (int i = 0; i < NM; ++i)
-            if (i == lane) rdg = Rc[i];
-          const double act_next = actv[(lane + 1 < q ? lane + 1 : 0)];
-          const double u_next = uact[(lane + 1 < q ? lane + 1 : 0)];
-          const double dropped = actv[l];
-          wave_sync();
-          if (lane < q - 1) {
-#pragma unroll
-            for (int i = 0; i < NM; ++i)
-              if (i <= lane) Rm[i * ldm + lane] = Rc[i];
-            Rdi[lane] = 1.0 / rdg;
-            if (lane >= l) {
-              actv[lane] = act_next;
-              uact[lane] = u_next;
-            }
-          }
-          store_j();
-          if (lane == 0) aflag[static_cast<int64_t>(dropped)] = 0.0;
-          --q;
-          GI_ACC(4);
-          update_y();
-          GI_ACC(5);
-          if (!zero_step) sp = -row_g(pr, y, z);  // the entering row's slack at the new point
-        }
-      }
-      status = 0;
-      it = steps;
-#ifdef CCMPC_QP_TRACE
-      GI_MARK(5);
-      if (tid == 0 && sc == 0)
-        printf("gi phases (10ns): H+chol %d L %d J+norms %d z0 %d loop %d (steps %d, q %d)\n"
-               "   loop: scan %d d+r %d dir+ratios %d add %d drop %d update_y %d\n",
-               int(gmark[1] - gmark[0]), int(gmark[2] - gmark[1]), int(gmark[3] - gmark[2]),
-               int(gmark[4] - gmark[3]), int(gmark[5] - gmark[4]), steps, q, int(gacc[0]),
-               int(gacc[1]), int(gacc[2]), int(gacc[3]), int(gacc[4]), int(gacc[5]));
-#endif
-#undef GI_MARK
-#undef GI_T0
-#undef GI_ACC
-      return true;
-    };
-    if (A.polish) gi_done = gi_solve();
-    if constexpr (GIONLY) {
-      if (!gi_done) status = kQpNeedIpm;  // the IPM pass launched next takes this scene
-    }
-  }
 
-#ifdef CCMPC_QP_TRACE
-  uint64_t tk2 = 0;
-#endif
-  // the IPM and the polish: compiled out of the active-set-only instance (its registers)
-  if constexpr (!GIONLY) {
-  for (; !gi_done && it <= A.max_iter; ++it) {
+  for (; it <= A.max_iter; ++it) {
     QP_MARK(0);
     // ---- I1: residual norms, mu, per-step sums for r_d and M -------------------------------
     double rpmax = 0.0, sl = 0.0;
     for (int64_t r = tid; r < mrows; r += NTH) {
       const double s = rw.s[r];
-      const double rp = row_g(r, y, z) + s;
+      const double rp = cx.row_g(r, y, z) + s;
       rw.rp[r] = rp;
       rw.is[r] = 1.0 / s;
       rpmax = fmax(rpmax, fabs(rp));
@@ -1846,6 +1582,17 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
       w01 = fma(wa0, a1, w01);
       w11 = fma(wr * a1, a1, w11);
     };
+    auto store_step = [&](int t) {  // step t's q and weights B_t from its sums
+      const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
+      const int64_t rv = nbox + 2 * t;
+      q[3 * t] = wp * y[3 * t] + qf[3 * t] + la0;  // H_pos z + f + G^T lambda, output space
+      q[3 * t + 1] = wp * y[3 * t + 1] + qf[3 * t + 1] + la1;
+      q[3 * t + 2] = rw.l[rv] - rw.l[rv + 1];
+      bw[4 * t] = wp + w00;
+      bw[4 * t + 1] = w01;
+      bw[4 * t + 2] = wp + w11;
+      bw[4 * t + 3] = rw.l[rv] * rw.is[rv] + rw.l[rv + 1] * rw.is[rv + 1];
+    };
     if constexpr (NW == 1) {
       // one wave, T <= 8: lanes (t, sub) = (lane >> 3, lane & 7), every step's sums at once
       const int t = lane >> 3, sub = lane & 7;
@@ -1856,17 +1603,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
       w00 = sum8(w00);
       w01 = sum8(w01);
       w11 = sum8(w11);
-      if (sub == 0 && t < T) {
-        const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
-        const int64_t rv = nbox + 2 * t;
-        q[3 * t] = wp * y[3 * t] + qf[3 * t] + la0;
-        q[3 * t + 1] = wp * y[3 * t + 1] + qf[3 * t + 1] + la1;
-        q[3 * t + 2] = rw.l[rv] - rw.l[rv + 1];
-        bw[4 * t] = wp + w00;
-        bw[4 * t + 1] = w01;
-        bw[4 * t + 2] = wp + w11;
-        bw[4 * t + 3] = rw.l[rv] * rw.is[rv] + rw.l[rv + 1] * rw.is[rv + 1];
-      }
+      if (sub == 0 && t < T) store_step(t);
     } else for (int t = w; t < T; t += NW) {
       la0 = la1 = w00 = w01 = w11 = 0.0;
       for_step(t, lane, 64, step_acc);
@@ -1875,17 +1612,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
       w00 = wave_sum(w00);
       w01 = wave_sum(w01);
       w11 = wave_sum(w11);
-      if (lane == 0) {
-        const double wp = 2.0 * (p.w_ref + (t == T - 1 ? p.w_final : 0.0));
-        const int64_t rv = nbox + 2 * t;
-        q[3 * t] = wp * y[3 * t] + qf[3 * t] + la0;  // H_pos z + f + G^T lambda, output space
-        q[3 * t + 1] = wp * y[3 * t + 1] + qf[3 * t + 1] + la1;
-        q[3 * t + 2] = rw.l[rv] - rw.l[rv + 1];
-        bw[4 * t] = wp + w00;
-        bw[4 * t + 1] = w01;
-        bw[4 * t + 2] = wp + w11;
-        bw[4 * t + 3] = rw.l[rv] * rw.is[rv] + rw.l[rv + 1] * rw.is[rv + 1];
-      }
+      if (lane == 0) store_step(t);
     }
     qp_sync<NW>();
     QP_MARK(1);
@@ -1925,7 +1652,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     mu = block_sum<NW>(sl, red) / static_cast<double>(mrows);
 #ifdef CCMPC_QP_TRACE
     const double tr_rp = rpmax, tr_rd = rdmax;
-    if (it == 0 && tid == 0 && sc == 0)
+    if (it == 0 && tid == 0 && cx.sc == 0)
       printf("qp it %d rp %.3e/%.3e rd %.3e/%.3e mu %.3e\n", it, tr_rp, tol_p, tr_rd, tol_d, mu);
 #endif
     if (it == 0) mu0 = mu;
@@ -1974,16 +1701,10 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     if (w == 0) {
       bool fail;
       if constexpr (NM > 0) {
-#pragma unroll
-        for (int k = 0; k < NR; ++k) {
-          const double v = M[(lane < n ? lane : 0) * ldm + (k < n ? k : 0)];
-          La[k] = (lane < n && k <= lane) ? v : (k == lane ? 1.0 : 0.0);
-        }
+        reg_load_lower(M, ldm, n, La);
         fail = reg_cholesky(La, Ldl);
         // L overwrites M's lower triangle (read by the L^T solves)
-#pragma unroll
-        for (int k = 0; k < NR; ++k)
-          if (k < n && lane < n && k <= lane) M[lane * ldm + k] = La[k];
+        reg_store_lower(M, ldm, n, La);
         wave_sync();
       } else {
         fail = wave_cholesky(M, n, ldm, dinv, true);
@@ -2007,14 +1728,13 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
       if constexpr (NM > 0) {
         const double b = reg_solve(La, M, ldm, Ldl, n, lane < n ? x[lane] : 0.0);
         if (lane < n) x[lane] = b;
-        if constexpr (NW == 1) {  // yd = Gs dz, dz read back by readlane (0 beyond n)
-          const int kk = lane < T3 ? lane : 0;
-          double v = 0.0;
+        // yd = Gs dz, dz read back by readlane (0 beyond n)
+        const int kk = lane < T3 ? lane : 0;
+        double v = 0.0;
 #pragma unroll
-          for (int j = 0; j < NM; ++j) v = fma(Gs[kk * n + (j < n ? j : 0)], lane_bcast(b, j), v);
-          if (lane < T3) yd[lane] = v;
-          wave_sync();
-        }
+        for (int j = 0; j < NM; ++j) v = fma(Gs[kk * n + (j < n ? j : 0)], lane_bcast(b, j), v);
+        if (lane < T3) yd[lane] = v;
+        wave_sync();
       } else {
         double b[2];
         wave_load2(x, n, b);
@@ -2040,29 +1760,25 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
         u0 = fma(u, oa0[o], u0);
         u1 = fma(u, oa1[o], u1);
       };
+      auto store = [&](int t) {
+        const int64_t rv = nbox + 2 * t;
+        q[3 * t] = u0;
+        q[3 * t + 1] = u1;
+        q[3 * t + 2] = urow(rv) - urow(rv + 1);
+      };
       if constexpr (NW == 1) {   // as I1: lanes (t, sub), every step at once
         const int t = lane >> 3, sub = lane & 7;
         u0 = u1 = 0.0;
         if (t < T) for_step_it(t, sub, 8, lane_it, acc);
         u0 = sum8(u0);
         u1 = sum8(u1);
-        if (sub == 0 && t < T) {
-          const int64_t rv = nbox + 2 * t;
-          q[3 * t] = u0;
-          q[3 * t + 1] = u1;
-          q[3 * t + 2] = urow(rv) - urow(rv + 1);
-        }
+        if (sub == 0 && t < T) store(t);
       } else for (int t = w; t < T; t += NW) {
         u0 = u1 = 0.0;
         for_step(t, lane, 64, acc);
         u0 = wave_sum(u0);
         u1 = wave_sum(u1);
-        if (lane == 0) {
-          const int64_t rv = nbox + 2 * t;
-          q[3 * t] = u0;
-          q[3 * t + 1] = u1;
-          q[3 * t + 2] = urow(rv) - urow(rv + 1);
-        }
+        if (lane == 0) store(t);
       }
       qp_sync<NW>();
       if constexpr (NW == 1) {  // quad per control, as rd
@@ -2107,7 +1823,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     };
     for (int64_t r = tid; r < mrows; r += NTH) {
       const double s = rw.s[r], l = rw.l[r], rp = rw.rp[r];
-      const double gd = row_gd(r, yd, dz);
+      const double gd = cx.row_gd(r, yd, dz);
       const double ds = -rp - gd, dl = l * rw.is[r] * (gd + rp) - l;
       rw.ds[r] = ds;
       rw.dl[r] = dl;
@@ -2133,7 +1849,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     aden = 1.0;
     for (int64_t r = tid; r < mrows; r += NTH) {
       const double s = rw.s[r], l = rw.l[r], rp = rw.rp[r];
-      const double gd = row_gd(r, yd, dz);
+      const double gd = cx.row_gd(r, yd, dz);
       const double rc = rc_of(r);
       const double ds = -rp - gd, dl = (-rc - l * ds) * rw.is[r];
       rw.ds[r] = ds;  // every read of this row's ds_aff / dl_aff happened above in this thread
@@ -2152,7 +1868,7 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
     qp_sync<NW>();
 #ifdef CCMPC_QP_TRACE
     QP_MARK(7);
-    if (tid == 0 && sc == 0)
+    if (tid == 0 && cx.sc == 0)
       printf("qp it %d rp %.3e rd %.3e mu %.3e alpha %.3e\n   t(10ns) I1 %d I2 %d chol %d "
              "pred_rhs %d pred_step %d corr_rhs %d corr_step %d\n", it, tr_rp, tr_rd, mu, alpha,
              int(tmark[1] - tmark[0]), int(tmark[2] - tmark[1]), int(tmark[3] - tmark[2]),
@@ -2162,62 +1878,21 @@ __global__ __launch_bounds__(64 * NW) void mpc_qp_kernel(QpArgs A) {
   }
 
 #ifdef CCMPC_QP_TRACE
-  tk2 = wall_clock64();
+  const uint64_t tk2 = wall_clock64();
 #endif
-  if (A.polish && !infeasible && !polished && !gi_done) polished = polish(true);
-  }
+  if (A.polish && !infeasible && !polished) polished = polish(true);
 #ifdef CCMPC_QP_TRACE
   const uint64_t tk3 = wall_clock64();
 #endif
-  // ---- outputs: u, X = Gamma_f u + const (all four state rows), the objective value ----------
-  for (int j = tid; j < n; j += NTH) A.out_u[sc * n + j] = z[j];
-  double part = 0.0;
-  for (int r = tid; r < 4 * T; r += NTH) {
-    const int gr = 4 * Tp + r;
-    const double *g = Gam + static_cast<int64_t>(gr) * ncol;
-    double x = xb[gr];
-    if (uprev)
-      for (int j = 0; j < 2 * Tp; ++j) x += g[j] * uprev[j];
-    for (int j = 0; j < n; ++j) x += g[2 * Tp + j] * (z[j] - (ubar ? ubar[2 * Tp + j] : 0.0));
-    A.out_x[sc * 4 * T + r] = x;
-    const int t = r / 4, a = r % 4;
-    if (a < 2) {  // compute_objective_referenceTraj (:2478-2507) at the solution
-      const int tr = t < A.n_ref ? t : A.n_ref - 1;
-      const double e = x - ref[2 * tr + a];
-      part += p.w_ref * e * e;
-      if (t == T - 1) {
-        const double ef = x - (a == 0 ? g0 : g1);
-        part += p.w_final * ef * ef;
-      }
-    }
-  }
-  for (int t = tid; t < T; t += NTH) {
-    const double a0 = z[u_index(t, 0, T, order)], a1 = z[u_index(t, 1, T, order)];
-    part += a0 * (p.w_accel * a0 + p.w_joint * a1) + a1 * (p.w_joint * a0 + p.w_turning * a1);
-    if (t >= 1) {
-      const double d0 = a0 - z[u_index(t - 1, 0, T, order)];
-      const double d1 = a1 - z[u_index(t - 1, 1, T, order)];
-      part += d0 * (p.w_ch_accel * d0 + p.w_ch_joint * d1) +
-              d1 * (p.w_ch_joint * d0 + p.w_ch_turning * d1);
-    }
-  }
-  const double cost = block_sum<NW>(part, red);
-  double sk = skipped;
-  double dummy = 0.0;
-  block_max2<NW>(sk, dummy, red);
-  if (tid == 0) {
-    A.out_cost[sc] = cost;
-    A.out_status[sc] = status | (sk > 0.0 ? CCMPC_QP_SKIPPED_ROWS : 0);
-    A.out_iter[sc] = it;
-  }
+  cx.output(status, it);
 #ifdef CCMPC_QP_TRACE
   const uint64_t tk4 = wall_clock64();
-  if (tid == 0 && sc == 0)
+  if (tid == 0 && cx.sc == 0)
     printf("qp setup (10ns): model %d rows %d f %d init %d\n"
            "qp phases (10ns): setup %d iterations %d polish %d outputs %d\n"
            "   polish (first round): H %d act %d factor %d W %d S %d z %d\n",
-           int(smark[0] - tk0), int(smark[1] - smark[0]), int(smark[2] - smark[1]),
-           int(smark[3] - smark[2]), int(tk1 - tk0),
+           int(cx.smark[0] - cx.tk0), int(cx.smark[1] - cx.smark[0]),
+           int(cx.smark[2] - cx.smark[1]), int(cx.smark[3] - cx.smark[2]), int(tk1 - cx.tk0),
            int(tk2 - tk1), int(tk3 - tk2), int(tk4 - tk3), int(pmark[1] - pmark[0]),
            int(pmark[2] - pmark[1]), int(pmark[3] - pmark[2]), int(pmark[4] - pmark[3]),
            int(pmark[5] - pmark[4]), int(pmark[6] - pmark[5]));
@@ -2240,19 +1915,45 @@ inline QpPlan qp_plan(int T, int64_t R) {
   return {false, false};
 }
 
-template <bool ROWS_LDS, int NM, int NW, bool GI = false, bool GIONLY = false>
-hipError_t launch_qp(dim3 grid, size_t lds, hipStream_t s, const QpArgs &a) {
-  const dim3 block(64 * NW);
+using QpKernel = void (*)(QpArgs);
+
+// the instance of either kernel for where the rows live
+template <int NM>
+QpKernel qp_gi_instance(bool rows_lds) {
+  return rows_lds ? mpc_qp_gi_kernel<true, NM> : mpc_qp_gi_kernel<false, NM>;
+}
+template <int NM, int NW>
+QpKernel qp_ipm_instance(bool rows_lds) {
+  return rows_lds ? mpc_qp_ipm_kernel<true, NM, NW> : mpc_qp_ipm_kernel<false, NM, NW>;
+}
+
+inline hipError_t launch_qp(QpKernel kernel, int waves, dim3 grid, size_t lds, hipStream_t s,
+                            const QpArgs &a) {
   // the dynamic-LDS limit is a per-device attribute: set it on every launch (cheap), so a
   // process that drives several devices raises it on each, and report a failure as such
   if (lds > 48 * 1024) {
     const hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void *>(mpc_qp_kernel<ROWS_LDS, NM, NW, GI, GIONLY>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kQpLdsBytes));
+        reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        static_cast<int>(kQpLdsBytes));
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((mpc_qp_kernel<ROWS_LDS, NM, NW, GI, GIONLY>), grid, block, lds, s, a);
+  hipLaunchKernelGGL(kernel, grid, dim3(64 * waves), lds, s, a);
   return hipSuccess;
+}
+
+// The per-call knobs of the environment (tests and A/B tools switch them between calls)
+inline void qp_env_knobs(QpArgs &a) {
+  const char *e = getenv("CCMPC_QP_METHOD");
+  a.method = (e && strcmp(e, "ipm") == 0) ? CCMPC_QP_METHOD_IPM
+             : (e && strcmp(e, "gi") == 0) ? CCMPC_QP_METHOD_GI : kQpDefaultMethod;
+  e = getenv("CCMPC_QP_GI_MAX_STEPS");  // test hook
+  a.gi_max_steps = e ? atoi(e) : -1;
+  e = getenv("CCMPC_QP_GI_NOSTEP");     // A/B and tests
+  a.gi_nostep = e ? atoi(e) : 2;
+  e = getenv("CCMPC_QP_EARLY_POLISH");  // a test switches it
+  const double v = e ? atof(e) : kEarlyPolish;
+  a.early = fabs(v);
+  a.early_discard = v < 0.0;
 }
 
 }  // namespace ccmpc
@@ -2326,23 +2027,7 @@ static int mpc_qp_impl(const ccmpc_qp_ltv *ltv, int64_t n_scenes, int64_t T, int
   a.max_iter = max_iter;
   a.rows_in_lds = in_lds;
   a.polish = plan.polish;
-  {
-    const char *e = getenv("CCMPC_QP_METHOD");  // per call (tests switch it)
-    a.method = (e && strcmp(e, "ipm") == 0) ? CCMPC_QP_METHOD_IPM
-               : (e && strcmp(e, "gi") == 0) ? CCMPC_QP_METHOD_GI : kQpDefaultMethod;
-  }
-  {
-    const char *e = getenv("CCMPC_QP_GI_MAX_STEPS");  // per call (test hook)
-    a.gi_max_steps = e ? atoi(e) : -1;
-    const char *ns = getenv("CCMPC_QP_GI_NOSTEP");    // per call (A/B and tests)
-    a.gi_nostep = ns ? atoi(ns) : 2;
-  }
-  {
-    const char *e = getenv("CCMPC_QP_EARLY_POLISH");  // per call (a test switches it)
-    const double v = e ? atof(e) : kEarlyPolish;
-    a.early = fabs(v);
-    a.early_discard = v < 0.0;
-  }
+  qp_env_knobs(a);
   a.max_cells = max_cells_per_scene;
   a.tol = tol;
   a.gamma = gamma;
@@ -2372,63 +2057,32 @@ static int mpc_qp_impl(const ccmpc_qp_ltv *ltv, int64_t n_scenes, int64_t T, int
     a.ltv_xbar = const_cast<double *>(xbar);
     a.ltv_gamma = const_cast<double *>(gamma);
   }
-  const size_t lds = static_cast<size_t>(QpLayout(Ti, in_lds ? R : 0, in_lds, plan.polish).total) *
-                     sizeof(double);
-  CCMPC_REQUIRE(lds <= kQpLdsBytes, "T too large for the LDS image");
   const int n = 2 * Ti;
-  // register-resident factor up to n = 16 (T <= 8, the reference's ph); larger n spills
-  const int nm = n <= 16 ? 16 : 0;
-  // one wave per scene with the register factor (n <= 16), unless CCMPC_QP_WAVES=4 asks for the
-  // four-wave form (A/B)
-  static const int waves_env = [] {
-    const char *e = getenv("CCMPC_QP_WAVES");
-    return e ? atoi(e) : 1;
-  }();
-  const bool one_wave = nm == 16 && waves_env == 1;
+  size_t lds = static_cast<size_t>(QpLayout(Ti, in_lds ? R : 0, in_lds, plan.polish).total) *
+               sizeof(double);
+  // The active-set solve's row prefetch past R: QpLayout's total already holds its reach; with
+  // the rows in the workspace a T <= 2 launch is sized with the same few doubles once more
+  if (!in_lds && 3 * n < 15) lds += (15 - 3 * n) * sizeof(double);
+  CCMPC_REQUIRE(lds <= kQpLdsBytes, "T too large for the LDS image");
   const dim3 grid(static_cast<unsigned>(n_scenes));
   hipStream_t s = as_stream(stream);
-  hipError_t attr;
-  const bool gi = one_wave && a.method == CCMPC_QP_METHOD_GI && plan.polish;
-  // a batch runs the active-set pass without the IPM's code in its instance (189 instead of
-  // 488 VGPRs, far fewer SGPR spills), then an IPM pass that solves only the scenes it handed
-  // over -- the IPM's own answer, byte for byte, as the combined instance's hand-over gives;
-  // a single scene keeps the combined instance (the second launch would cost it more)
-  // (CCMPC_QP_GI_SPLIT: 0 never, 1 batches -- the default --, 2 a single scene too)
-  const char *se = getenv("CCMPC_QP_GI_SPLIT");
-  const int split_env = se ? atoi(se) : 1;
-  // n = 17 .. 32 (T = 9 .. 16): the active-set pass on one wave (factor and J in registers,
-  // 32 per lane), then the four-wave IPM pass for the scenes it handed over
-  const bool gi32 = n > 16 && n <= 32 && a.method == CCMPC_QP_METHOD_GI && plan.polish;
-  if (gi32) {
-    attr = in_lds ? launch_qp<true, 32, 1, true, true>(grid, lds, s, a)
-                  : launch_qp<false, 32, 1, true, true>(grid, lds, s, a);
-    if (attr == hipSuccess) {
-      QpArgs f = a;
-      f.fallback_only = 1;
-      attr = in_lds ? launch_qp<true, 0, 4>(grid, lds, s, f)
-                    : launch_qp<false, 0, 4>(grid, lds, s, f);
-    }
-  } else if (gi && split_env > 0 && (n_scenes > 1 || split_env > 1)) {
-    attr = in_lds ? launch_qp<true, 16, 1, true, true>(grid, lds, s, a)
-                  : launch_qp<false, 16, 1, true, true>(grid, lds, s, a);
-    if (attr == hipSuccess) {
-      QpArgs f = a;
-      f.fallback_only = 1;
-      attr = in_lds ? launch_qp<true, 16, 1>(grid, lds, s, f)
-                    : launch_qp<false, 16, 1>(grid, lds, s, f);
-    }
-  } else if (gi) {
-    attr = in_lds ? launch_qp<true, 16, 1, true>(grid, lds, s, a)
-                  : launch_qp<false, 16, 1, true>(grid, lds, s, a);
-  } else if (in_lds) {
-    attr = one_wave ? launch_qp<true, 16, 1>(grid, lds, s, a)
-                    : (nm == 16 ? launch_qp<true, 16, 4>(grid, lds, s, a)
-                                : launch_qp<true, 0, 4>(grid, lds, s, a));
-  } else {
-    attr = one_wave ? launch_qp<false, 16, 1>(grid, lds, s, a)
-                    : (nm == 16 ? launch_qp<false, 16, 4>(grid, lds, s, a)
-                                : launch_qp<false, 0, 4>(grid, lds, s, a));
+  // The IPM: one wave per scene with the register-resident factor up to n = 16 (T <= 8, the
+  // reference's ph; larger n spills), else four waves.
+  // The active-set pass (n <= 32, T <= 16; it lives in the polish's blocks): one wave, factor
+  // and J in registers, 16 or 32 per lane.  It runs as a launch of its own, without the IPM's
+  // code in its instance (197 VGPRs against the IPM's 256 + 190 AGPRs, far fewer SGPR spills),
+  // then the IPM pass solves only the scenes it handed over -- the IPM's own answer, byte for
+  // byte.  A single scene too: its second launch costs less than the combined instance's
+  // registers did (35.4 against 36.6 us for the T = 8 solve, profiles/r19/README.md).
+  const bool gi = a.method == CCMPC_QP_METHOD_GI && n <= 32 && plan.polish;
+  const QpKernel ipm = n <= 16 ? qp_ipm_instance<16, 1>(in_lds) : qp_ipm_instance<0, 4>(in_lds);
+  hipError_t attr = hipSuccess;
+  if (gi) {
+    const QpKernel gik = n <= 16 ? qp_gi_instance<16>(in_lds) : qp_gi_instance<32>(in_lds);
+    attr = launch_qp(gik, 1, grid, lds, s, a);
+    a.fallback_only = 1;
   }
+  if (attr == hipSuccess) attr = launch_qp(ipm, n <= 16 ? 1 : 4, grid, lds, s, a);
   if (attr != hipSuccess) {
     set_error(std::string(__func__) + ": hipFuncSetAttribute(MaxDynamicSharedMemorySize) "
               "failed: " + hipGetErrorString(attr));

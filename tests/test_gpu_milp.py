@@ -1,6 +1,6 @@
 """v8's MILP (v8/__init__.py:692-838): the big-M obstacle disjunction over the
 L4 faces with v8's compute_objective, solved on the GPU by ccmpc.milp.BranchAndBound (batched
-mpc_qp_kernel launches per round) against the oracle's exact optimum (oracle/mpc_oracle.py
+ccmpc_mpc_qp calls, one per round) against the oracle's exact optimum (oracle/mpc_oracle.py
 milp_bnb, SciPy QPs; milp_enumerate over every face assignment where that is small).
 
 Parity bar: the MILP optimum is unique on these scenes, so u within 1e-6 (1 + |u|), the cost

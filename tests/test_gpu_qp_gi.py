@@ -24,9 +24,8 @@ def _solve(monkeypatch, method, cps, T, kind, order, gamma, xbar, goals, refs, r
 @pytest.mark.parametrize("order", [mpc.U_ORDER_F, mpc.U_ORDER_C])
 @pytest.mark.parametrize("T", [8, 12, 16])
 def test_gi_equals_ipm_on_many_scenes(gpu, monkeypatch, kind, order, T):
-    """T = 8: the 16-per-lane instance (the combined GI + IPM instance for a batch's hand-overs
-    is not used: the GI-only pass, then the one-wave IPM pass); T = 12 / 16: the 32-per-lane
-    GI-only instance, then the four-wave IPM pass."""
+    """T = 8: the 16-per-lane active-set kernel, then the one-wave IPM pass for its hand-overs;
+    T = 12 / 16: the 32-per-lane active-set kernel, then the four-wave IPM pass."""
     seeds = list(range(100, 148)) if T <= 12 else list(range(100, 124))
     rec, cps, o_recs, refs, goals, x0s = _scene_inputs(seeds, T, gpu, kind=kind)
     xbar, gamma = mpc.ltv(x0s, T, lon=LON)
@@ -88,10 +87,11 @@ def test_gi_shrinking_horizon_with_executed_controls(gpu, monkeypatch):
 @pytest.mark.parametrize("T", [8, 12])
 def test_gi_hands_over_to_the_ipm(gpu, monkeypatch, T):
     """A solve that exceeds the active-set step budget (forced here: CCMPC_QP_GI_MAX_STEPS=0)
-    hands the problem to the IPM in the same launch from the setup's state: the scenes that
-    needed an active-set change come back as the IPM alone returns them, byte for byte, the
+    hands the problem to the IPM pass launched next, which starts from its own setup: the scenes
+    that needed an active-set change come back as the IPM alone returns them, byte for byte, the
     others (the unconstrained minimum is feasible) agree to round-off.  T = 12: the hand-over
-    is from the 32-per-lane GI-only instance to the four-wave IPM pass."""
+    is from the 32-per-lane active-set kernel to the four-wave IPM pass.  T = 8 also hands over
+    a single scene solved on its own, the path a one-scene planner takes."""
     from ccmpc import mpc
     seeds = list(range(40, 52))
     rec, cps, _, refs, goals, x0s = _scene_inputs(seeds, T, gpu, "halfspace")
@@ -103,14 +103,14 @@ def test_gi_hands_over_to_the_ipm(gpu, monkeypatch, T):
     # finished" is exactly "GI solved it"
     monkeypatch.setenv("CCMPC_QP_GI_NOSTEP", "1")
 
-    def run(method, steps=None):
+    def run(method, steps=None, cps=cps, inputs=(gamma, xbar, goal, ref, rec)):
         monkeypatch.setenv("CCMPC_QP_METHOD", method)
         if steps is None:
             monkeypatch.delenv("CCMPC_QP_GI_MAX_STEPS", raising=False)
         else:
             monkeypatch.setenv("CCMPC_QP_GI_MAX_STEPS", str(steps))
         qp = mpc.PlanningQP(cps, T, device=gpu)
-        out = qp.solve(gamma, xbar, goal, ref, rec)
+        out = qp.solve(*inputs)
         return [t.cpu().numpy().copy() for t in out]
 
     ipm = run("ipm")
@@ -134,6 +134,15 @@ def test_gi_hands_over_to_the_ipm(gpu, monkeypatch, T):
                 handed_mid += budget > 0
         assert handed > 0, budget
     assert handed_mid > 0            # some hand-over came after rows had entered
+    if T == 8:
+        # the same for a single QP (no batch around it): the first scene that needs an
+        # active-set change, alone, handed over at once
+        s = next(s for s in range(len(seeds)) if not (gi_done[s] and gi[4][s] == 0))
+        c = sum(cps[:s])
+        one = (gamma[s:s + 1], xbar[s:s + 1], goal[s:s + 1], ref[s:s + 1],
+               rec[c:c + cps[s]].contiguous())
+        ipm1, forced1 = run("ipm", None, [cps[s]], one), run("gi", 0, [cps[s]], one)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(forced1, ipm1))
 
 
 def test_gi_verdict_on_near_parallel_rows(gpu, monkeypatch):
