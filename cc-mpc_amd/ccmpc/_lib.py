@@ -161,6 +161,8 @@ SIGNATURES = {
     "ccmpc_face_constraints": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64,
                                               _I64, _P, _P, _P, _P, _P, ctypes.c_int, _D, _P,
                                               _SZ, _P, _P]),
+    "ccmpc_face_audit": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64, _I64, _P,
+                                        _P, _D, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ccmpc_face_cuts": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _P, _D, _P, _I64, _I32, _I32, _D,
                                        _I32, _P, _P, _P, _P, _P, _P]),
     "ccmpc_selftest": (ctypes.c_int, [ctypes.c_int, _I64, _P, _P, _D, _I32, _P]),

@@ -843,6 +843,124 @@ def risk_audit(store, plan=None, rec=None, rec_kind=None, R=risk.R_COLLISION, ce
     return out
 
 
+FaceAudit = collections.namedtuple(
+    "FaceAudit", "face_open in_box in_box_any sel_open sel_open_any worst")
+FaceAudit.__doc__ = """face_audit's device tensors: face_open [C, T, 4], in_box [C, T], in_box_any
+[C] int64; sel_open [C, T], sel_open_any [C] int64 (None without face_sel); worst [C, T, 4]
+float64 (None with worst=False).  See ccmpc_face_audit in include/ccmpc.h for what each counts."""
+
+
+def face_audit(store, past_last, plan, face_sel=None, cell_plan=None, extent=(3.7, 1.79),
+               car_r=4.47213, T=None, ld_plan=None, worst=True, out=None):
+    """Monte-Carlo audit of the box-face rows on a ParticleStore (ccmpc_face_audit): per
+    (cell, t) the particles each face's inequality leaves open at `plan`, those inside whose
+    inflated box the plan lies, the count under the selected face and the largest violation.
+
+    past_last [C, 2] and extent = (lon, lat) as face_constraints (host arrays, or contiguous
+    float64 device tensors, which are read in place).  plan: ego positions in the first two
+    columns -- a host array (T, >= 2) / (n_plans, T, >= 2), copied as [n, T, 2], or a contiguous
+    float64 device tensor [n_plans, T, ld_plan >= 2] read in place (PlanningSOCP's X [S, T, 4]);
+    ld_plan overrides the step stride of a flat device tensor.  cell_plan: each cell's plan row
+    (None: row 0), a host sequence (range-checked here) or an int32 device tensor [C].
+    face_sel [C, T]: 0..3 the face that is the row of (c, t), -1 no row; a host array
+    (range-checked here: ValueError outside [-1, 3]) or a contiguous int32 device tensor; None
+    skips the two sel outputs.  T: the audited horizon (default store.T).  worst=False skips the
+    maxima.  out: a previous FaceAudit whose buffers are written again (with device-resident
+    inputs nothing is allocated then, so the call can be captured).
+    Returns FaceAudit; enqueues two launches on the current stream, never synchronises."""
+    lib = _lib.load()
+    dev = store.device
+    C = store.n_cells
+    T = store.T if T is None else int(T)
+    if not 1 <= T <= store.T:
+        raise ValueError(f"T = {T} outside [1, {store.T}] (the store's horizon)")
+    if getattr(store, "offsets", None) and any(int(o) % 4 for o in store.offsets):
+        raise ValueError("cell offsets must be multiples of 4 particles")
+    f64 = dict(dtype=torch.float64, device=dev)
+
+    def small(x, shape, name):
+        if torch.is_tensor(x):
+            if (x.dtype != torch.float64 or x.device != dev or not x.is_contiguous()
+                    or x.numel() != int(np.prod(shape))):
+                raise ValueError(f"{name} must be a contiguous float64 {shape} tensor on {dev}")
+            return x
+        return torch.as_tensor(np.ascontiguousarray(x, np.float64).reshape(shape), **f64)
+    pl = small(past_last, (C, 2), "past_last")
+    ex = small(extent, (2,), "extent")
+    if torch.is_tensor(plan) and plan.device == dev:
+        t_plan = plan
+        if t_plan.dtype != torch.float64 or not t_plan.is_contiguous():
+            raise ValueError("a device plan must be a contiguous float64 tensor")
+        if ld_plan is None:
+            if t_plan.dim() == 2:
+                t_plan = t_plan.unsqueeze(0)
+            if t_plan.dim() != 3 or t_plan.shape[1] != T or t_plan.shape[2] < 2:
+                raise ValueError(f"plan must be ({T}, >= 2) or (n_plans, {T}, >= 2)")
+            ld_plan = int(t_plan.shape[2])
+        ld_plan = int(ld_plan)
+        if ld_plan < 2 or t_plan.numel() % (T * ld_plan):
+            raise ValueError(f"plan holds no whole number of [{T}, {ld_plan}] rows")
+        n_plans = t_plan.numel() // (T * ld_plan)
+    else:
+        host = np.asarray(plan.cpu() if torch.is_tensor(plan) else plan, np.float64)
+        if host.ndim == 2:
+            host = host[None]
+        if host.ndim != 3 or host.shape[1] < T or host.shape[2] < 2:
+            raise ValueError(f"plan must be (T, >= 2) or (n_plans, T, >= 2) with T >= {T}")
+        if ld_plan is not None and int(ld_plan) != 2:
+            raise ValueError("ld_plan applies to a device plan; a host plan is copied as [n, T, 2]")
+        t_plan = torch.as_tensor(np.ascontiguousarray(host[:, :T, :2]), **f64)
+        ld_plan, n_plans = 2, int(host.shape[0])
+    if cell_plan is None:
+        if n_plans != 1:
+            raise ValueError(f"{n_plans} plans need cell_plan")
+    elif torch.is_tensor(cell_plan):        # device-resident: its range is the caller's contract
+        if (cell_plan.dtype != torch.int32 or tuple(cell_plan.shape) != (C,)
+                or cell_plan.device != dev or not cell_plan.is_contiguous()):
+            raise ValueError(f"cell_plan must be a contiguous int32 [{C}] tensor on {dev}")
+    else:
+        host = np.asarray(cell_plan, np.int64).reshape(-1)
+        if host.shape[0] != C or (C and (host.min() < 0 or host.max() >= n_plans)):
+            raise ValueError(f"cell_plan must hold {C} indices in [0, {n_plans})")
+        cell_plan = torch.as_tensor(host.astype(np.int32), device=dev)
+    if face_sel is not None:
+        if torch.is_tensor(face_sel) and face_sel.device == dev:
+            if (face_sel.dtype != torch.int32 or face_sel.numel() != C * T
+                    or not face_sel.is_contiguous()):
+                raise ValueError(f"face_sel must be a contiguous int32 [{C}, {T}] tensor")
+        else:
+            host = np.asarray(face_sel.cpu() if torch.is_tensor(face_sel) else face_sel, np.int64)
+            if host.shape != (C, T):
+                raise ValueError(f"face_sel must be ({C}, {T})")
+            if host.size and (host.min() < -1 or host.max() > 3):
+                raise ValueError("face_sel must be in [-1, 3]: a face 0..3, or -1 for no row")
+            face_sel = torch.as_tensor(np.ascontiguousarray(host.astype(np.int32)), device=dev)
+    on_s = face_sel is not None
+    want = dict(face_open=((C, T, 4), torch.int64, True), in_box=((C, T), torch.int64, True),
+                in_box_any=((C,), torch.int64, True), sel_open=((C, T), torch.int64, on_s),
+                sel_open_any=((C,), torch.int64, on_s),
+                worst=((C, T, 4), torch.float64, bool(worst)))
+    if out is None:
+        out = FaceAudit(*(torch.empty(shape, dtype=dt, device=dev) if on else None
+                          for shape, dt, on in want.values()))
+    else:
+        for name, (shape, dt, on) in want.items():
+            t = getattr(out, name)
+            if on and (t is None or tuple(t.shape) != shape or t.dtype != dt
+                       or not t.is_contiguous()):
+                raise ValueError(f"out.{name} must be a contiguous {dt} {shape} tensor")
+    if C == 0:
+        return out
+    _lib.check(lib.ccmpc_face_audit(
+        _p(store.pos), store.ccmpc_dtype, store.ld, T, _p(store.origin), _p(store.cell_off),
+        _p(store.cell_cnt), C, store.n_bound, _p(pl), _p(ex), float(car_r), _p(t_plan), ld_plan,
+        _p(cell_plan), _p(face_sel), _p(out.face_open), _p(out.in_box), _p(out.in_box_any),
+        _p(out.sel_open if on_s else None), _p(out.sel_open_any if on_s else None),
+        _p(out.worst if worst else None), _stream()), "ccmpc_face_audit")
+    out.face_open._keepalive = (pl, ex, t_plan, cell_plan, face_sel)
+    return out
+
+
 RiskQuantile = collections.namedtuple("RiskQuantile", "q rhs status workspace")
 RiskQuantile.__doc__ = """risk_quantile's device tensors: q [C, P] float64 (the (m+1)-th largest
 projection), rhs [C, P] float64 (the offset that protects it), status [C, P] int32 (0, or

@@ -161,6 +161,7 @@ class HalfSpaceList:
 
 
 CAR_R = 4.47213   # v8ideal/__init__.py:978 ("this is actually a diameter")
+FACE_EXTENT = (3.7, 1.79)   # truck_d = (lon, lat) of the box-face rows (:976-977)
 
 
 class SocConstraint:
@@ -622,6 +623,7 @@ class MidlevelAgent:
         self._audit_src = None             # (scene, K, T, _last_rec or None) of the last graph step
         self._face_src = None              # (scene, K, T, face records, gamma, rows) of the last
         #                                    box-face generator (solve_planning_socp's source)
+        self._face_audit_src = None        # (past_last [C, 2], extent) of it, for audit_face_rows
         self._last_sbig = False            # do its rows carry S_big (road boundaries)?
         self._qp_request = None            # the frame's QP inputs, set before its step graph
         self._qp_pending = None            # ((run, gen), records, (T, u_order)) enqueued
@@ -1159,15 +1161,17 @@ class MidlevelAgent:
         gamma = self._cell_risk_host(np.asarray(eps_ura), K)[:, 2]
         ref = self._ref(ref_traj, scene.T) if variant == "approx" else None
         mean, cov = engine.moments(scene.store, workspace=self._ws)
+        past_last = scene.cell_past_last()
         rec = engine.face_constraints(
-            scene.store, scene.cell_past_last(), gamma,
+            scene.store, past_last, gamma,
             kind="robust" if variant == "robust" else "nominal", ref_traj=ref,
-            car_r=CAR_R, workspace=self._face_workspace())
+            extent=FACE_EXTENT, car_r=CAR_R, workspace=self._face_workspace())
         h = engine.face_records(rec)
         self.last_records = h
         self._last_rec = None
         self._audit_src = None
         self._face_src = None
+        self._face_audit_src = None
         mean0 = mean[:, 0, :].cpu().numpy()
         cov0 = cov[:, 0:2, 0:2].cpu().numpy()
         last = mean0[_last_cells(tuple(K))].tolist()             # last mode wins (:1008-1019)
@@ -1176,6 +1180,8 @@ class MidlevelAgent:
                                   0.5 * CAR_R)
         # what solve_planning_socp and audit_face_plan read: the cone rows' own consumers
         self._face_src = (scene, list(K), T, rec, gamma, cons)
+        # and what audit_face_rows needs beside it to form the particles' headings and boxes
+        self._face_audit_src = (np.array(past_last, np.float64), FACE_EXTENT)
         st_mean, st_cov = self._state_stats(scene, mean0, cov0)
         vertices, A_union, b_union = self._l4_lists(scene)
         return (cons, vertices, A_union, b_union, any(gate), _object_grid(scene.O), st_mean,
@@ -1720,6 +1726,28 @@ class MidlevelAgent:
         plan = torch.as_tensor(np.ascontiguousarray(X[None, :, :2]), device=self.device)
         a = engine.risk_audit(scene.store, plan=plan, R=self.R if R is None else float(R), T=T)
         return risk.audit_report(a, scene.store.counts, K, self.prediction_horizon)
+
+    def audit_face_rows(self, X_star, faces=None):
+        """Monte-Carlo audit of the box-face rows of the last box-face generator call on the
+        particles they were built from (engine.face_audit): per (cell, t) the particles each
+        face's inequality leaves open at X_star (Tsh, >= 2), those inside whose inflated box the
+        plan lies, and the count under the selected row -- the empirical fraction to set beside
+        the eps_ura / Tpred the rows' Gamma was sized for.  The selection is
+        solve_planning_socp's (_face_selection): approx's own choice, or `faces`; nominal /
+        robust rows without `faces` raise the same ValueError; the cells of ungated OVs carry
+        no row (-1).  Returns risk.face_audit_report's dict and changes no planner state."""
+        if getattr(self, "_face_src", None) is None:
+            raise RuntimeError("no face records: call a box-face generator first")
+        scene, K, T, rec, _, cons = self._face_src
+        past_last, extent = self._face_audit_src
+        scene.check_live()
+        X = np.asarray(X_star, np.float64)
+        if X.ndim != 2 or X.shape[0] != T or X.shape[1] < 2:
+            raise ValueError(f"X_star must be ({T}, >= 2) for the face step's Tsh = {T}")
+        sel = self._face_selection(cons, rec.shape[0], T, faces)
+        a = engine.face_audit(scene.store, past_last, X[None, :, :2], face_sel=sel,
+                              extent=extent, car_r=CAR_R, T=T)
+        return risk.face_audit_report(a, scene.store.counts, K, self.prediction_horizon)
 
     def calibrate_constraints(self, R=None, eps=None, mode=None):
         """Monte-Carlo calibration of the last predict_and_constrain /

@@ -117,6 +117,57 @@ def audit_report(audit, counts, K, ph, eps=EPS_TOTAL):
     return out
 
 
+def face_audit_report(audit, counts, K, ph, eps=EPS_TOTAL):
+    """Host-side report of an engine.FaceAudit (device tensors or arrays) against the risk
+    budget the face rows' Gamma was sized for: counts [n_cells] particles per cell, K modes per
+    OV (cells in (ov, k) order), ph the horizon the per-step budget is split over.  Reports
+    only: it judges nothing beyond the within_budget booleans and changes no planner decision.
+    Returns a dict of NumPy arrays --
+      face_open [C, T, 4], in_box [C, T], in_box_any [C], sel_open [C, T] (-1: no row),
+      sel_open_any [C], worst [C, T, 4]   the audit's own arrays (None for a part not run)
+      p_face_open [C, T, 4], p_in_box [C, T], p_in_box_any [C]   counts over N_c (nan for an
+                                          empty cell)
+      p_sel_open [C, T]                   sel_open / N_c, nan where (c, t) has no row
+      p_sel_open_any [C]                  sel_open_any / N_c
+      has_row [C, T]                      sel_open >= 0 (None without face_sel)
+      counts [C] = N_c, budget_traj [C] = eps_ura[o, k], budget_step [C] = eps_ura[o, k] / ph
+      step_within_budget [C, T]  p_sel_open <= budget_step   (False where there is no row or no
+                                 particle; None without face_sel)
+      traj_within_budget [C]     p_sel_open_any <= budget_traj (False for an empty cell)
+      row_holds [C, T, 4]        worst <= 0: row f holds for every particle (None without worst)
+      worst_row (cell, t)        the row with the largest p_sel_open (None without one),
+      worst_p_sel_open           its value."""
+    K = [int(k) for k in K]
+    n = np.asarray(counts, np.float64).reshape(-1)
+    if n.shape[0] != sum(K):
+        raise ValueError(f"{n.shape[0]} cell counts for {sum(K)} cells")
+    budget_traj, budget_step = _cell_budgets(K, ph, eps)
+    face_open, in_box, in_box_any = _np(audit.face_open), _np(audit.in_box), _np(audit.in_box_any)
+    sel_open, sel_open_any, worst = _np(audit.sel_open), _np(audit.sel_open_any), _np(audit.worst)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = np.where(n > 0, n, np.nan)
+        out = dict(face_open=face_open, in_box=in_box, in_box_any=in_box_any, sel_open=sel_open,
+                   sel_open_any=sel_open_any, worst=worst,
+                   p_face_open=face_open / den[:, None, None], p_in_box=in_box / den[:, None],
+                   p_in_box_any=in_box_any / den, p_sel_open=None, p_sel_open_any=None,
+                   has_row=None, counts=n.astype(np.int64), budget_traj=budget_traj,
+                   budget_step=budget_step, step_within_budget=None, traj_within_budget=None,
+                   row_holds=None if worst is None else worst <= 0.0, worst_row=None,
+                   worst_p_sel_open=None)
+        if sel_open is not None:
+            has_row = sel_open >= 0
+            p_sel = np.where(has_row, sel_open / den[:, None], np.nan)
+            p_any = sel_open_any / den
+            out.update(has_row=has_row, p_sel_open=p_sel, p_sel_open_any=p_any,
+                       step_within_budget=p_sel <= budget_step[:, None],
+                       traj_within_budget=p_any <= budget_traj)
+            if p_sel.size and not np.all(np.isnan(p_sel)):
+                c, t = np.unravel_index(int(np.nanargmax(p_sel)), p_sel.shape)
+                out["worst_row"] = (int(c), int(t))
+                out["worst_p_sel_open"] = float(p_sel[c, t])
+    return out
+
+
 def allow_counts(counts, K, ph, eps=EPS_TOTAL):
     """(n_cells,) int64 = floor(eps_ura[o, k] / ph * N_c): the particles of cell c a record may
     leave open without exceeding the per-step budget audit_report sets its counts beside

@@ -3,6 +3,7 @@
 
 #include "audit.hpp"
 #include "ccmpc_common.hpp"
+#include "face_audit.hpp"
 #include "faces.hpp"
 #include "quantile.hpp"
 #include "socp.hpp"
@@ -331,6 +332,49 @@ extern "C" int ccmpc_face_constraints(const void *positions, int dtype, int64_t 
   a.rec = out_rec;
   const int rc = ccmpc::launch_face_constraints(a, n_particles_bound, workspace,
                                                 ccmpc::as_stream(stream));
+  CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
+  CCMPC_LAUNCH_CHECK();
+  return CCMPC_OK;
+}
+
+// ---- Monte-Carlo audit of the box-face rows (face_audit.hip) ---------------------------------
+extern "C" int ccmpc_face_audit(const void *positions, int dtype, int64_t ld, int64_t T,
+                                const double *origin, const int64_t *cell_off,
+                                const int64_t *cell_cnt, int64_t n_cells,
+                                int64_t n_particles_bound, const double *past_last,
+                                const double *extent, double car_r, const double *plan,
+                                int64_t ld_plan, const int32_t *cell_plan,
+                                const int32_t *face_sel, int64_t *out_face_open,
+                                int64_t *out_in_box, int64_t *out_in_box_any,
+                                int64_t *out_sel_open, int64_t *out_sel_open_any,
+                                double *out_worst, ccmpc_stream_t stream) {
+  CCMPC_REQUIRE(T >= 1 && T <= ccmpc::kAuditMaxT, "T must be in [1, 40]");
+  CCMPC_REQUIRE(std::isfinite(car_r), "car_r must be finite");
+  CCMPC_REQUIRE(ld_plan >= 2, "ld_plan must be >= 2");
+  CCMPC_REQUIRE(n_cells >= 0 && n_cells < (1 << 30), "bad n_cells");
+  CCMPC_REQUIRE(n_particles_bound >= 0, "bad n_particles_bound");
+  CCMPC_REQUIRE(dtype == CCMPC_F64 || dtype == CCMPC_F32, "bad dtype");
+  CCMPC_REQUIRE(ld % 4 == 0 && ld > 0, "ld must be a positive multiple of 4");
+  CCMPC_REQUIRE(positions && cell_off && cell_cnt && past_last && extent && plan, "null pointer");
+  CCMPC_REQUIRE(out_face_open && out_in_box && out_in_box_any,
+                "out_face_open, out_in_box and out_in_box_any are required");
+  CCMPC_REQUIRE(!face_sel || (out_sel_open && out_sel_open_any),
+                "face_sel needs out_sel_open and out_sel_open_any");
+  CCMPC_REQUIRE(ccmpc::aligned(positions, 16), "positions must be 16-byte aligned");
+  CCMPC_REQUIRE(ccmpc::aligned(plan, 8) && ccmpc::aligned(past_last, 8) &&
+                    ccmpc::aligned(extent, 8),
+                "plan, past_last and extent must be 8-byte aligned");
+  CCMPC_REQUIRE(ccmpc::aligned(out_face_open, 8) && ccmpc::aligned(out_in_box, 8) &&
+                    ccmpc::aligned(out_in_box_any, 8) && ccmpc::aligned(out_sel_open, 8) &&
+                    ccmpc::aligned(out_sel_open_any, 8) && ccmpc::aligned(out_worst, 8),
+                "outputs must be 8-byte aligned");
+  if (n_cells == 0) return CCMPC_OK;
+  const ccmpc::FaceAuditArgs a{positions, dtype, ld, static_cast<int>(T), origin, cell_off,
+                               cell_cnt, static_cast<int>(n_cells), n_particles_bound, past_last,
+                               extent, car_r, plan, ld_plan, cell_plan, face_sel, out_face_open,
+                               out_in_box, out_in_box_any, face_sel ? out_sel_open : nullptr,
+                               face_sel ? out_sel_open_any : nullptr, out_worst};
+  const int rc = ccmpc::launch_face_audit(a, ccmpc::as_stream(stream));
   CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
   CCMPC_LAUNCH_CHECK();
   return CCMPC_OK;

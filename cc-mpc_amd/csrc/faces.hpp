@@ -34,6 +34,33 @@ struct FaceArgs {
   ccmpc_face_rec *rec;       // [c][T][4]
 };
 
+// cos / sin of the heading of a step delta, as l4.hip's heading_cs_rsq forms them (restated, so
+// that file keeps its bits): (dx, dy) / |(dx, dy)| from the hardware rsqrt with two Newton steps;
+// a delta whose squared norm would be subnormal is first scaled by 2^600 (exact); a zero step or
+// an overflowing norm keeps sincos of atan2 (atan2(0, 0) = 0: c = 1, s = 0).
+__device__ __forceinline__ void face_heading(double dx, double dy, double &S, double &C) {
+  double n2 = dx * dx + dy * dy;
+  if (n2 < 0x1p-960) {
+    dx *= 0x1p600;
+    dy *= 0x1p600;
+    n2 = dx * dx + dy * dy;
+  }
+  if (n2 > 0.0 && n2 < INFINITY) {
+    double r = __builtin_amdgcn_rsq(n2);
+    r = r * fma(-0.5 * n2 * r, r, 1.5);
+    r = r * fma(-0.5 * n2 * r, r, 1.5);
+    C = dx * r;
+    S = dy * r;
+  } else {
+    sincos(atan2(dy, dx), &S, &C);
+  }
+}
+
+template <typename P>
+__device__ __forceinline__ double face_world(P v, double o) {
+  return static_cast<double>(v) + o;  // as world() in l4.hip
+}
+
 inline size_t face_round256(size_t b) { return (b + 255) / 256 * 256; }
 
 // Workspace: first | head | part, each 256-byte aligned.  `items` = max_items at the chunk used.

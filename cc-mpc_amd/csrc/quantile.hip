@@ -45,17 +45,6 @@ constexpr int kQuantThreads = 256;
 constexpr int kQuantSingle = 0x100;  // one candidate left: the next pass stores its key in rank[]
 constexpr int kQuantDone = 0x200;    // prefix is q's whole key
 constexpr int kQuantU = 4;  // steps per load group
-constexpr uint64_t kSignBit = uint64_t(1) << 63;
-constexpr uint64_t kKeyNegInf = ~0xFFF0000000000000ull;            // key of -inf
-constexpr uint64_t kKeyPosInf = 0x7FF0000000000000ull | kSignBit;  // key of +inf
-
-__device__ __forceinline__ uint64_t quant_key(double w) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, w);
-  return (b >> 63) ? ~b : (b | kSignBit);
-}
-__device__ __forceinline__ double quant_unkey(uint64_t k) {
-  return __builtin_bit_cast(double, (k >> 63) ? (k & ~kSignBit) : ~k);
-}
 
 // First launch: statuses, the outputs of records that select nothing, the staged records, the
 // ranks and empty bins.

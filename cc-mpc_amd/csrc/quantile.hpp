@@ -9,6 +9,20 @@ namespace ccmpc {
 constexpr int kQuantDigits = 8;     // 8-bit digits of the 64-bit key, most significant first
 constexpr int kQuantMaxChunk = 32;  // records per counting workgroup: 1 KiB of LDS bins each
 
+// The order-preserving 64-bit key of a double: unsigned key order = value order (-0 below +0).
+// The radix select works on it; the face audit (face_audit.hip) takes its maxima on it.
+constexpr uint64_t kSignBit = uint64_t(1) << 63;
+constexpr uint64_t kKeyNegInf = ~0xFFF0000000000000ull;            // key of -inf
+constexpr uint64_t kKeyPosInf = 0x7FF0000000000000ull | kSignBit;  // key of +inf
+
+__device__ __forceinline__ uint64_t quant_key(double w) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, w);
+  return (b >> 63) ? ~b : (b | kSignBit);
+}
+__device__ __forceinline__ double quant_unkey(uint64_t k) {
+  return __builtin_bit_cast(double, (k >> 63) ? (k & ~kSignBit) : ~k);
+}
+
 // A record as the counting passes read it (written by the call's first launch, its prefix
 // extended by every narrowing launch).  t < 0: nothing to select (VACUOUS or SKIPPED); else the
 // step in the low byte and the selection state above it (quantile.hip).

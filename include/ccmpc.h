@@ -830,6 +830,71 @@ int ccmpc_face_constraints(const void *positions, int dtype, int64_t ld, int64_t
                            size_t workspace_bytes, ccmpc_face_rec *out_rec, ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Monte-Carlo audit of the box-face rows on the particles they were built from: of the
+ * particles of (cell, t), how many violate face f's inequality at a plan?  The companion of
+ * ccmpc_risk_audit for the cone rows (no reference counterpart): the analytic row bounds that
+ * fraction by eps_ura / Tpred under a Gaussian assumption, this call counts it.  One streaming
+ * pass over planes 0 .. 2T-1 of the store (T may be smaller than the horizon the store holds).
+ *
+ * Store arguments (positions .. n_particles_bound), past_last and extent = {lon, lat} are those
+ * of ccmpc_face_constraints, with the same F32 rule (double)rel + origin[c].
+ *  plan[r][T][ld_plan]  ego positions: x, y = the first two of each step's ld_plan doubles
+ *                       (ld_plan = 4 reads ccmpc_mpc_qp's out_x in place, as ccmpc_face_cuts;
+ *                       ld_plan >= 2)
+ *  cell_plan[c]         the plan row cell c is audited against (NULL -> row 0)
+ *  face_sel[c][T]       nullable.  0..3: that face is the row of (c, t); any other value: (c, t)
+ *                       has no row (the cells of ungated OVs, -1 in the planner)
+ *
+ * Per particle of cell c at step t, in float64, with no contraction, products before sums:
+ *   (x, y)  its world position;  (c, s) the unit vector of its step delta exactly as
+ *           ccmpc_face_constraints forms it (step 0 from past_last, a zero step gives c = 1,
+ *           s = 0)
+ *   ex = X - x,  ey = Y - y                     (X, Y) = plan[cell_plan[c]][t]
+ *   p  = c*ex - s*ey,   q = s*ex + c*ey
+ *   hlat = 0.5*lat + 0.5*car_r,   hlon = 0.5*lon + 0.5*car_r
+ *   v0 = hlat - p,  v1 = hlon - q,  v2 = hlat + p,  v3 = hlon + q
+ * In exact arithmetic v_f = a_f . (X, Y, 1) + 0.5 car_r with a1..a4 of ccmpc_face_constraints;
+ * the relative form avoids the cancellation of the ~200 m terms.  Face f's inequality holds for
+ * the particle iff v_f <= 0; the particle is open under face f iff v_f > 0 (strict).
+ *
+ * Outputs, all written in full by every call (the caller initialises nothing):
+ *  out_face_open[c][T][4]  particles of the cell with v_f > 0
+ *  out_in_box[c][T]        particles with all four v_f > 0: the ego point lies inside that
+ *                          particle's inflated box, so no choice of face protects it
+ *  out_in_box_any[c]       particles in the box at any t < T
+ *  out_sel_open[c][T]      out_face_open at the selected face; -1 where (c, t) has no row
+ *  out_sel_open_any[c]     particles open under the selected row at any step that has one: the
+ *                          event the per-mode budget eps_ura bounds, which the rows split by
+ *                          / Tpred; 0 if no step has a row
+ *  out_worst[c][T][4]      the largest v_f over the cell's particles, -inf for an empty cell:
+ *                          the shift that would make row f hold for every particle; <= 0 iff the
+ *                          row holds for all of them
+ * face_sel == NULL skips the two sel outputs (their pointers may then be NULL); out_worst may be
+ * NULL and is then skipped; the other three outputs are required.
+ *
+ * CCMPC_ERR_ARG, all checked on the host before any launch: T outside [1, 40], ld not a positive
+ * multiple of 4, ld_plan < 2, car_r not finite, n_cells < 0, a NULL positions, cell_off,
+ * cell_cnt, past_last, extent, plan or required output, a non-NULL face_sel with a NULL sel
+ * output.  cell_off entries must be multiples of 4, as for ccmpc_moments;
+ * n_particles_bound >= sum(cell_cnt) sizes the grid; counts and offsets are read on the device.
+ * Two launches (initial values, then the pass), no workspace, no host synchronisation: the call
+ * is capturable.  Counts are integer atomics.  out_worst is an unsigned 64-bit atomic maximum on
+ * the order-preserving key of the double (ccmpc_risk_quantile's key), applied to the double's
+ * own bits: a signed integer maximum for a sign-clear pattern, an unsigned integer minimum for a
+ * sign-set one, each of which raises the stored pattern's key to the larger of the two.  No
+ * output bit depends on execution order.  Positions are assumed finite; non-finite ones give
+ * unspecified values but no out-of-range access.
+ * ------------------------------------------------------------------------------------- */
+int ccmpc_face_audit(const void *positions, int dtype, int64_t ld, int64_t T,
+                     const double *origin, const int64_t *cell_off, const int64_t *cell_cnt,
+                     int64_t n_cells, int64_t n_particles_bound, const double *past_last,
+                     const double *extent, double car_r, const double *plan, int64_t ld_plan,
+                     const int32_t *cell_plan, const int32_t *face_sel,
+                     int64_t *out_face_open, int64_t *out_in_box, int64_t *out_in_box_any,
+                     int64_t *out_sel_open, int64_t *out_sel_open_any, double *out_worst,
+                     ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Outer-approximation (Kelley) cuts of the box-face cone rows: what turns ccmpc_face_rec rows
  * into records ccmpc_mpc_qp reads.  The reference hands the rows to cvxpy / CPLEX as
  * second-order cones (v8ideal/__init__.py:1353-1363); with one face fixed per (cell, t) -- the
