@@ -19,7 +19,7 @@ CCMPC_F32 = 1
 GMM_PER_LATENT, GMM_PER_PARTICLE = 0, 1
 # record kinds (CCMPC_REC_KIND_*)
 REC_KIND_HALFSPACE, REC_KIND_AFFINE, REC_KIND_HALFSPACE_COMPACT, REC_KIND_AFFINE_COMPACT = range(4)
-# ccmpc_risk_quantile's out_status (CCMPC_CAL_*; 0: calibrated)
+# ccmpc_risk_quantile's and ccmpc_face_quantile's out_status (CCMPC_CAL_*; 0: calibrated)
 CAL_VACUOUS, CAL_SKIPPED = 1, 2
 # ccmpc_gather_rec, the 32-byte compact packing of either record kind
 GATHER_DTYPE = np.dtype([("n0", "<f8"), ("n1", "<f8"), ("rhs", "<f8"), ("side", "<i2"),
@@ -163,6 +163,10 @@ SIGNATURES = {
                                               _SZ, _P, _P]),
     "ccmpc_face_audit": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64, _I64, _P,
                                         _P, _D, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ccmpc_face_quantile_workspace_bytes": (_SZ, [_I64, _I64]),
+    "ccmpc_face_quantile": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64, _I64,
+                                           _P, _P, _D, _P, _I64, _P, _P, _D, _P, _SZ, _P, _P, _P,
+                                           _P, _P]),
     "ccmpc_face_cuts": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _P, _D, _P, _I64, _I32, _I32, _D,
                                        _I32, _P, _P, _P, _P, _P, _P]),
     "ccmpc_selftest": (ctypes.c_int, [ctypes.c_int, _I64, _P, _P, _D, _I32, _P]),

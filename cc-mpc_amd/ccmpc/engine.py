@@ -843,32 +843,9 @@ def risk_audit(store, plan=None, rec=None, rec_kind=None, R=risk.R_COLLISION, ce
     return out
 
 
-FaceAudit = collections.namedtuple(
-    "FaceAudit", "face_open in_box in_box_any sel_open sel_open_any worst")
-FaceAudit.__doc__ = """face_audit's device tensors: face_open [C, T, 4], in_box [C, T], in_box_any
-[C] int64; sel_open [C, T], sel_open_any [C] int64 (None without face_sel); worst [C, T, 4]
-float64 (None with worst=False).  See ccmpc_face_audit in include/ccmpc.h for what each counts."""
-
-
-def face_audit(store, past_last, plan, face_sel=None, cell_plan=None, extent=(3.7, 1.79),
-               car_r=4.47213, T=None, ld_plan=None, worst=True, out=None):
-    """Monte-Carlo audit of the box-face rows on a ParticleStore (ccmpc_face_audit): per
-    (cell, t) the particles each face's inequality leaves open at `plan`, those inside whose
-    inflated box the plan lies, the count under the selected face and the largest violation.
-
-    past_last [C, 2] and extent = (lon, lat) as face_constraints (host arrays, or contiguous
-    float64 device tensors, which are read in place).  plan: ego positions in the first two
-    columns -- a host array (T, >= 2) / (n_plans, T, >= 2), copied as [n, T, 2], or a contiguous
-    float64 device tensor [n_plans, T, ld_plan >= 2] read in place (PlanningSOCP's X [S, T, 4]);
-    ld_plan overrides the step stride of a flat device tensor.  cell_plan: each cell's plan row
-    (None: row 0), a host sequence (range-checked here) or an int32 device tensor [C].
-    face_sel [C, T]: 0..3 the face that is the row of (c, t), -1 no row; a host array
-    (range-checked here: ValueError outside [-1, 3]) or a contiguous int32 device tensor; None
-    skips the two sel outputs.  T: the audited horizon (default store.T).  worst=False skips the
-    maxima.  out: a previous FaceAudit whose buffers are written again (with device-resident
-    inputs nothing is allocated then, so the call can be captured).
-    Returns FaceAudit; enqueues two launches on the current stream, never synchronises."""
-    lib = _lib.load()
+def _face_plan_inputs(store, past_last, plan, cell_plan, extent, T, ld_plan):
+    """The checked device inputs face_audit and face_quantile share (see face_audit):
+    (T, past_last, extent, plan, ld_plan, cell_plan)."""
     dev = store.device
     C = store.n_cells
     T = store.T if T is None else int(T)
@@ -923,6 +900,39 @@ def face_audit(store, past_last, plan, face_sel=None, cell_plan=None, extent=(3.
         if host.shape[0] != C or (C and (host.min() < 0 or host.max() >= n_plans)):
             raise ValueError(f"cell_plan must hold {C} indices in [0, {n_plans})")
         cell_plan = torch.as_tensor(host.astype(np.int32), device=dev)
+    return T, pl, ex, t_plan, ld_plan, cell_plan
+
+
+FaceAudit = collections.namedtuple(
+    "FaceAudit", "face_open in_box in_box_any sel_open sel_open_any worst")
+FaceAudit.__doc__ = """face_audit's device tensors: face_open [C, T, 4], in_box [C, T], in_box_any
+[C] int64; sel_open [C, T], sel_open_any [C] int64 (None without face_sel); worst [C, T, 4]
+float64 (None with worst=False).  See ccmpc_face_audit in include/ccmpc.h for what each counts."""
+
+
+def face_audit(store, past_last, plan, face_sel=None, cell_plan=None, extent=(3.7, 1.79),
+               car_r=4.47213, T=None, ld_plan=None, worst=True, out=None):
+    """Monte-Carlo audit of the box-face rows on a ParticleStore (ccmpc_face_audit): per
+    (cell, t) the particles each face's inequality leaves open at `plan`, those inside whose
+    inflated box the plan lies, the count under the selected face and the largest violation.
+
+    past_last [C, 2] and extent = (lon, lat) as face_constraints (host arrays, or contiguous
+    float64 device tensors, which are read in place).  plan: ego positions in the first two
+    columns -- a host array (T, >= 2) / (n_plans, T, >= 2), copied as [n, T, 2], or a contiguous
+    float64 device tensor [n_plans, T, ld_plan >= 2] read in place (PlanningSOCP's X [S, T, 4]);
+    ld_plan overrides the step stride of a flat device tensor.  cell_plan: each cell's plan row
+    (None: row 0), a host sequence (range-checked here) or an int32 device tensor [C].
+    face_sel [C, T]: 0..3 the face that is the row of (c, t), -1 no row; a host array
+    (range-checked here: ValueError outside [-1, 3]) or a contiguous int32 device tensor; None
+    skips the two sel outputs.  T: the audited horizon (default store.T).  worst=False skips the
+    maxima.  out: a previous FaceAudit whose buffers are written again (with device-resident
+    inputs nothing is allocated then, so the call can be captured).
+    Returns FaceAudit; enqueues two launches on the current stream, never synchronises."""
+    lib = _lib.load()
+    dev = store.device
+    C = store.n_cells
+    T, pl, ex, t_plan, ld_plan, cell_plan = _face_plan_inputs(store, past_last, plan, cell_plan,
+                                                              extent, T, ld_plan)
     if face_sel is not None:
         if torch.is_tensor(face_sel) and face_sel.device == dev:
             if (face_sel.dtype != torch.int32 or face_sel.numel() != C * T
@@ -959,6 +969,91 @@ def face_audit(store, past_last, plan, face_sel=None, cell_plan=None, extent=(3.
         _p(out.worst if worst else None), _stream()), "ccmpc_face_audit")
     out.face_open._keepalive = (pl, ex, t_plan, cell_plan, face_sel)
     return out
+
+
+FaceQuantile = collections.namedtuple("FaceQuantile", "q arg cut status")
+FaceQuantile.__doc__ = """face_quantile's device tensors: q [C, T, 4] float64 (the (m+1)-th largest
+face value), arg [C, T, 4] int64 (the particle that attains it, -1 for none), cut [C, T, 4, 32]
+uint8 (ccmpc_gather_rec: that particle's half-space shifted to the budget, or an empty record),
+status [C, T] int32 (0, or _lib.CAL_VACUOUS / CAL_SKIPPED).  See ccmpc_face_quantile in
+include/ccmpc.h."""
+
+_face_quantile_ws = {}      # (device, stream) -> the call's workspace, grown on demand
+
+
+def face_quantile(store, past_last, plan, allow=None, cell_plan=None, extent=(3.7, 1.79),
+                  car_r=4.47213, margin=0.0, T=None, ld_plan=None, out=None, workspace=None):
+    """Monte-Carlo calibration of the box-face rows on a ParticleStore (ccmpc_face_quantile):
+    per (cell, t, face) the (allow[c] + 1)-th largest face value v_f of the cell's particles at
+    `plan` -- the distance by which the row misses (> 0) or clears (<= 0) a budget of allow[c]
+    open particles --, the particle that attains it, and that particle's own half-space shifted
+    to the budget and by `margin`, as a record the planning QP reads.
+
+    store, past_last, plan, cell_plan, extent, car_r, T and ld_plan as face_audit.  allow as
+    risk_quantile: None (zeros), a host sequence (checked to be >= 0 here) or an int64 device
+    tensor [C] (read unchecked; a negative entry marks the cell SKIPPED), e.g.
+    risk.allow_counts.  margin >= 0.  out: a previous FaceQuantile whose buffers are written
+    again.  workspace: a uint8 device tensor of ccmpc_face_quantile_workspace_bytes(T, C) bytes;
+    None takes one cached per (device, stream), as PlanningQP keeps its own (with `out`, a given
+    workspace and device-resident inputs nothing is allocated, so the call can be captured).
+    Returns FaceQuantile; enqueues 19 launches on the current stream, never synchronises."""
+    lib = _lib.load()
+    dev = store.device
+    C = store.n_cells
+    T, pl, ex, t_plan, ld_plan, cell_plan = _face_plan_inputs(store, past_last, plan, cell_plan,
+                                                              extent, T, ld_plan)
+    margin = float(margin)
+    if not (np.isfinite(margin) and margin >= 0.0):
+        raise ValueError("margin must be finite and >= 0")
+    if allow is None:
+        pass
+    elif torch.is_tensor(allow):
+        if (allow.dtype != torch.int64 or tuple(allow.shape) != (C,) or allow.device != dev
+                or not allow.is_contiguous()):
+            raise ValueError(f"allow must be a contiguous int64 [{C}] tensor on {dev}")
+    else:
+        host = np.asarray(allow, np.int64).reshape(-1)
+        if host.shape[0] != C or (C and host.min() < 0):
+            raise ValueError(f"allow must hold {C} counts >= 0")
+        allow = torch.as_tensor(host, device=dev)
+    need = int(lib.ccmpc_face_quantile_workspace_bytes(T, C))
+    if need == 0:
+        raise ValueError(f"ccmpc_face_quantile rejects T = {T}, n_cells = {C}")
+    want = dict(q=((C, T, 4), torch.float64), arg=((C, T, 4), torch.int64),
+                cut=((C, T, 4, 32), torch.uint8), status=((C, T), torch.int32))
+    if out is None:
+        out = FaceQuantile(*(torch.empty(shape, dtype=dt, device=dev)
+                             for shape, dt in want.values()))
+    else:
+        for name, (shape, dt) in want.items():
+            t = getattr(out, name)
+            if t is None or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"out.{name} must be a contiguous {dt} {shape} tensor")
+    if workspace is None:
+        stream = _stream()
+        key = (dev, int(getattr(stream, "value", stream) or 0))
+        workspace = _face_quantile_ws.get(key)
+        if workspace is None or workspace.numel() < need:
+            workspace = _face_quantile_ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif (workspace.dtype != torch.uint8 or workspace.device != dev
+          or not workspace.is_contiguous() or workspace.numel() < need):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of {need} bytes on {dev}")
+    if C == 0:
+        return out
+    _lib.check(lib.ccmpc_face_quantile(
+        _p(store.pos), store.ccmpc_dtype, store.ld, T, _p(store.origin), _p(store.cell_off),
+        _p(store.cell_cnt), C, store.n_bound, _p(pl), _p(ex), float(car_r), _p(t_plan), ld_plan,
+        _p(cell_plan), _p(allow), margin, _p(workspace), workspace.numel(), _p(out.q),
+        _p(out.arg), _p(out.cut), _p(out.status), _stream()), "ccmpc_face_quantile")
+    out.q._keepalive = (pl, ex, t_plan, cell_plan, allow, workspace)
+    return out
+
+
+def face_quantile_cuts(quant):
+    """Host view of a FaceQuantile's cut records: a structured array [C, T, 4] of
+    _lib.GATHER_DTYPE (n0, n1, rhs, side, status, t_tau)."""
+    b = quant.cut.detach().cpu().numpy() if torch.is_tensor(quant.cut) else np.asarray(quant.cut)
+    return np.ascontiguousarray(b).view(_lib.GATHER_DTYPE)[..., 0]
 
 
 RiskQuantile = collections.namedtuple("RiskQuantile", "q rhs status workspace")

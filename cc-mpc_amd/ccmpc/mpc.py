@@ -275,6 +275,97 @@ class PlanningSOCP:
                           np.array(costs).reshape(-1, S))
 
 
+TIGHTEN_OK = 0             # every selected row leaves at most allow[c] particles open (q <= 0)
+TIGHTEN_INFEASIBLE = 1     # a tightening QP returned QP_MAXITER: the pool's rows are infeasible
+TIGHTEN_NUMERIC = 2        # QP_NUMERIC, passed through
+TIGHTEN_MAXROUNDS = 8      # max_rounds QPs solved, some selected q still above 0
+
+TightenResult = collections.namedtuple("TightenResult", "u X cost status rounds margins costs")
+TightenResult.__doc__ = """PlanningTighten.solve's answer: u [1, 2T], X [1, T, 4], cost [1] device
+tensors of the last plan; status (TIGHTEN_*); rounds (tightening QPs solved); margins
+[rounds + 1, C, T] NumPy: the selected row's q at the SOCP plan and after every tightening QP
+(nan without a row); costs [rounds] the QP cost of every tightening round."""
+
+
+class PlanningTighten:
+    """Monte-Carlo tightening of one scene's box-face plan to a particle budget: one more
+    cutting-plane loop of PlanningSOCP.solve's pattern, on sample cuts instead of Kelley cuts.
+    From the plan a solved PlanningSOCP left, every round is one engine.face_quantile at the
+    current X (per selected row the distance q by which it misses a budget of allow[c] open
+    particles, and the half-space on which the particle that attains q is protected, shifted
+    by `margin`), the non-empty cuts of the selected faces appended to a pool that also keeps
+    every cone cut of the SOCP's final round set, one PlanningQP over that pool, and one small
+    read-back.  It ends when every selected q <= 0 (TIGHTEN_OK), when a QP is infeasible, or
+    after max_rounds QPs.  `margin` is what lets a QP that holds its rows to ~1e-9 reach q <= 0
+    exactly.
+
+    Where all particles of a cell share a heading, q is affine in the plan and the sample cut is
+    exact: the loop is Kelley's method on a polyhedron.  With differing headings the set
+    {x : q(x) <= 0} is not convex in general (the particle that attains q changes with the plan,
+    and each particle's face turns with its own heading): the loop is then a heuristic that may
+    cut off plans that would meet the budget, and may end in MAXROUNDS or INFEASIBLE where such a
+    plan exists.  One scene (socp.S == 1)."""
+
+    def __init__(self, socp, max_rounds=8):
+        if socp.S != 1:
+            raise ValueError("PlanningTighten handles one scene")
+        if max_rounds < 1:
+            raise ValueError("max_rounds must be >= 1")
+        self.socp, self.max_rounds = socp, int(max_rounds)
+        C, T = socp.n_cells, socp.T
+        self.base = (socp.max_rounds + 1) * C           # the SOCP pool's cells
+        cells = self.base + self.max_rounds * C
+        self.qp = PlanningQP([cells], T, socp.qp.T_full, kind=REC_AFFINE_COMPACT,
+                             params=socp.qp.params, u_order=socp.qp.u_order,
+                             device=socp.device)
+        dev = self.device = socp.device
+        self.pool = torch.empty((max(cells, 1), T, 32), dtype=torch.uint8, device=dev)
+        empty = np.zeros((1, T), _lib.GATHER_DTYPE)
+        empty["side"], empty["status"], empty["t_tau"] = -1, _lib.CUT_EMPTY, np.arange(T)
+        self.empty = torch.as_tensor(empty.view(np.uint8).reshape(1, T, 32), device=dev)
+
+    def solve(self, store, past_last, allow, face_sel, gamma, xbar, goal, ref, u_prev=None,
+              extent=(3.7, 1.79), margin=1e-6):
+        """After self.socp.solve(...) ended SOCP_OK: store / past_last / extent / allow as
+        engine.face_quantile; face_sel int32 [C, T] device tensor (-1: no row); gamma .. u_prev
+        as the PlanningQP.solve calls the SOCP made (the LTV model is read, not rebuilt).
+        Returns TightenResult; synchronises once per round."""
+        socp, C, T, base = self.socp, self.socp.n_cells, self.socp.T, self.base
+        self.pool[:base] = socp.pool[:base]
+        self.pool[base:] = self.empty
+        has = face_sel >= 0
+        idx = face_sel.clamp(0, 3).to(torch.int64)
+        u, X, cost = socp.u, socp.X, socp.cost
+        status, rounds, margins, costs = TIGHTEN_MAXROUNDS, 0, [], []
+        for rnd in range(self.max_rounds + 1):
+            quant = engine.face_quantile(store, past_last, X, allow=allow, extent=extent,
+                                         car_r=socp.car_r, margin=margin, T=T)
+            q = torch.gather(quant.q, 2, idx[..., None])[..., 0]
+            q = torch.where(has, q, torch.full_like(q, float("nan")))
+            margins.append(q.cpu().numpy())
+            if not np.any(margins[-1] > 0.0):
+                status = TIGHTEN_OK
+                break
+            if rnd == self.max_rounds:
+                break
+            cut = torch.gather(quant.cut, 2, idx[..., None, None].expand(C, T, 1, 32))[:, :, 0]
+            self.pool[base + rnd * C:base + (rnd + 1) * C] = torch.where(
+                has[..., None], cut, self.empty)
+            u, X, cost, qstat, _ = self.qp.solve(gamma, xbar, goal, ref, self.pool,
+                                                 u_prev=u_prev)
+            back = torch.stack((qstat.to(torch.float64), cost)).cpu().numpy()
+            rounds = rnd + 1
+            costs.append(float(back[1, 0]))
+            qs = int(back[0, 0]) & ~QP_SKIPPED_ROWS
+            if qs == QP_MAXITER:
+                status = TIGHTEN_INFEASIBLE
+                break
+            if qs == QP_NUMERIC:
+                status = TIGHTEN_NUMERIC
+                break
+        return TightenResult(u, X, cost, status, rounds, np.array(margins), np.array(costs))
+
+
 class PlanningQPStep:
     """One scene's planning QP as the planner calls it every frame, with its host traffic in
     two pinned packs (ccmpc/step.py's Pack): the frame's x_init, reference, goal and executed

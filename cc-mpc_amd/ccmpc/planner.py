@@ -1749,6 +1749,89 @@ class MidlevelAgent:
                               extent=extent, car_r=CAR_R, T=T)
         return risk.face_audit_report(a, scene.store.counts, K, self.prediction_horizon)
 
+    def calibrate_face_rows(self, X_star, faces=None, eps=None, margin=0.0):
+        """Monte-Carlo calibration of the box-face rows of the last box-face generator call on
+        the particles they were built from (engine.face_quantile): per (cell, t, face) the
+        distance by which the row misses (> 0) or clears (<= 0), at X_star (Tsh, >= 2), the
+        per-step budget of risk.allow_counts(...) open particles (eps default: risk.EPS_TOTAL)
+        -- how far the plan audit_face_rows counted is from meeting the budget.  The selection
+        is audit_face_rows' (_face_selection).  Returns risk.face_calibration_report's dict
+        plus `face_sel` and `cut` (engine.face_quantile_cuts' host records, shifted by
+        `margin`) and changes no planner state."""
+        if getattr(self, "_face_src", None) is None:
+            raise RuntimeError("no face records: call a box-face generator first")
+        scene, K, T, rec, _, cons = self._face_src
+        past_last, extent = self._face_audit_src
+        scene.check_live()
+        X = np.asarray(X_star, np.float64)
+        if X.ndim != 2 or X.shape[0] != T or X.shape[1] < 2:
+            raise ValueError(f"X_star must be ({T}, >= 2) for the face step's Tsh = {T}")
+        sel = self._face_selection(cons, rec.shape[0], T, faces)
+        eps = risk.EPS_TOTAL if eps is None else float(eps)
+        ph = self.prediction_horizon
+        counts = scene.store.counts
+        allow = risk.allow_counts(counts, K, ph, eps)
+        quant = engine.face_quantile(scene.store, past_last, X[None, :, :2], allow=allow,
+                                     extent=extent, car_r=CAR_R, margin=margin, T=T)
+        report = risk.face_calibration_report(quant, counts, K, ph, face_sel=sel, eps=eps)
+        report.update(face_sel=sel, cut=engine.face_quantile_cuts(quant))
+        return report
+
+    def tighten_face_plan(self, x_init, goal, ref_traj, Tsh, u_prev=None, lon=3.7,
+                          u_order=mpc.U_ORDER_F, faces=None, socp_rounds=12, tol_g=1e-6,
+                          max_rounds=8, margin=1e-6, eps=None):
+        """solve_planning_socp's plan, tightened until the particles themselves meet the
+        per-step budget: solve_planning_socp (unchanged; x_init .. tol_g are its arguments,
+        socp_rounds its max_rounds), then mpc.PlanningTighten on the particles of the last
+        box-face generator call -- engine.face_quantile at the current plan, the non-empty
+        sample cuts of the selected faces appended to the SOCP's final cut pool, the planning
+        QP again, until every selected row leaves at most risk.allow_counts(...) particles open
+        (q <= 0 exactly; `margin` metres are added to every cut so that a QP holding its rows to
+        ~1e-9 gets there).  A heuristic where the headings of a cell's particles differ (the
+        budget set is then not convex, see mpc.PlanningTighten); exact where they agree.
+        Returns solve_planning_socp's dict (the tightened plan's values) plus `tighten_rounds`
+        (QPs solved after the SOCP), `margins` [tighten_rounds + 1, C, T] (the selected row's q
+        at the SOCP plan and after every round, nan without a row) and `socp` (the untightened
+        dict).  Raises InSimulationException -- with `status` (mpc.TIGHTEN_*), `tighten_rounds`
+        and `margins` attributes -- where a tightening QP is infeasible or max_rounds do not
+        reach the budget.  Changes no planner state beyond what solve_planning_socp does."""
+        first = self.solve_planning_socp(x_init, goal, ref_traj, Tsh, u_prev=u_prev, lon=lon,
+                                         u_order=u_order, faces=faces, max_rounds=socp_rounds,
+                                         tol_g=tol_g)
+        scene, K, T, rec, _, cons = self._face_src
+        past_last, extent = self._face_audit_src
+        scene.check_live()
+        C, ph, dev = rec.shape[0], self.prediction_horizon, self.device
+        sel = self._face_selection(cons, C, T, faces)
+        socp = self._socp[(C, T, u_order, int(socp_rounds), float(tol_g))]
+        cache = self.__dict__.setdefault("_tighten", {})
+        key = (id(socp), int(max_rounds))
+        run = cache.get(key)
+        if run is None or run.socp is not socp:
+            run = cache[key] = mpc.PlanningTighten(socp, max_rounds=max_rounds)
+        eps = risk.EPS_TOTAL if eps is None else float(eps)
+        allow = risk.allow_counts(scene.store.counts, K, ph, eps)
+        xbar, gam = self._ltv_buffers()
+        f64 = dict(dtype=torch.float64, device=dev)
+        ref = torch.as_tensor(np.asarray(ref_traj, np.float64)[:T, :2].reshape(1, T, 2).copy(),
+                              **f64)
+        g2 = torch.as_tensor(np.asarray(goal, np.float64).reshape(1, 2), **f64)
+        up = None if T == ph else torch.as_tensor(
+            np.asarray(u_prev, np.float64).reshape(1, 2 * (ph - T)), **f64)
+        res = run.solve(scene.store, past_last, allow, torch.as_tensor(sel, device=dev), gam,
+                        xbar, g2, ref, u_prev=up, extent=extent, margin=margin)
+        if res.status != mpc.TIGHTEN_OK:
+            e = InSimulationException("Optimizer failed to find a solution")
+            e.status, e.tighten_rounds, e.margins = res.status, res.rounds, res.margins
+            raise e
+        out = dict(first)
+        if res.rounds:
+            u = res.u[0].cpu().numpy()
+            out.update(cost=float(res.cost[0].item()), U_star=run.qp.U(res.u)[0].cpu().numpy(),
+                       X_star=res.X[0].cpu().numpy(), u=u)
+        out.update(tighten_rounds=res.rounds, margins=res.margins, socp=first)
+        return out
+
     def calibrate_constraints(self, R=None, eps=None, mode=None):
         """Monte-Carlo calibration of the last predict_and_constrain /
         predict_and_constrain_affine frame's records on its sampled scene

@@ -178,6 +178,50 @@ def allow_counts(counts, K, ph, eps=EPS_TOTAL):
     return np.floor(_cell_budgets(K, ph, eps)[1] * n).astype(np.int64)
 
 
+def face_calibration_report(quant, counts, K, ph, face_sel=None, eps=EPS_TOTAL):
+    """Host-side report of an engine.FaceQuantile (device tensors or arrays) computed with
+    allow = allow_counts(counts, K, ph, eps): counts [n_cells], K and ph as face_audit_report;
+    face_sel [C, T]: 0..3 the face that is the row of (c, t), anything else no row (None: no
+    selected-row entries).  Reports only.  Returns a dict of NumPy arrays --
+      q [C, T, 4], arg [C, T, 4], status [C, T]   the call's own arrays (status 0 selected,
+                                1 vacuous: allow >= N_c, 2 skipped)
+      counts [C], budget_step [C] = eps_ura[o, k] / ph, allow [C] = allow_counts(...)
+      meets_budget [C, T, 4]    q <= 0: face f's row leaves at most allow particles open
+      margin_sel [C, T]         q at the selected face, in metres: by how far the row misses
+                                (> 0) or clears (<= 0) the budget; -inf for a vacuous row, nan
+                                without a row, for a skipped one and for an empty cell (None
+                                without face_sel)
+      step_meets_budget [C, T]  margin_sel <= 0 (False where it is nan)
+      worst_row (cell, t)       the row with the largest margin_sel (None without one),
+      worst_margin              its value."""
+    n = np.asarray(counts, np.float64).reshape(-1)
+    q, arg = _np(quant.q), _np(quant.arg)
+    status = _np(quant.status).astype(np.int64)
+    C, T = status.shape
+    if n.shape[0] != C:
+        raise ValueError(f"{n.shape[0]} cell counts for {C} cells")
+    with np.errstate(invalid="ignore"):
+        out = dict(q=q, arg=arg, status=status, counts=n.astype(np.int64),
+                   budget_step=_cell_budgets(K, ph, eps)[1], allow=allow_counts(n, K, ph, eps),
+                   meets_budget=q <= 0.0, margin_sel=None, step_meets_budget=None,
+                   worst_row=None, worst_margin=None)
+        if face_sel is not None:
+            sel = np.asarray(_np(face_sel), np.int64)
+            if sel.shape != (C, T):
+                raise ValueError(f"face_sel must be ({C}, {T})")
+            # a vacuous row of a cell with particles clears any budget (q = -inf); an empty cell
+            # has no fraction to meet one with, as in face_audit_report
+            has = (sel >= 0) & (sel <= 3) & (status != 2) & (n > 0)[:, None]
+            qs = np.take_along_axis(q, np.clip(sel, 0, 3)[..., None], -1)[..., 0]
+            m = np.where(has, qs, np.nan)
+            out.update(margin_sel=m, step_meets_budget=m <= 0.0)
+            if m.size and not np.all(np.isnan(m)):
+                c, t = np.unravel_index(int(np.nanargmax(m)), m.shape)
+                out["worst_row"] = (int(c), int(t))
+                out["worst_margin"] = float(m[c, t])
+    return out
+
+
 def calibration_report(quant, fields, counts, K, ph, eps=EPS_TOTAL):
     """Host-side report of an engine.RiskQuantile (device tensors or arrays) beside the analytic
     records it calibrated.  fields: the records' (n0, n1, rhs, side, ...) arrays [C, P]

@@ -4,6 +4,7 @@
 #include "audit.hpp"
 #include "ccmpc_common.hpp"
 #include "face_audit.hpp"
+#include "face_quantile.hpp"
 #include "faces.hpp"
 #include "quantile.hpp"
 #include "socp.hpp"
@@ -375,6 +376,83 @@ extern "C" int ccmpc_face_audit(const void *positions, int dtype, int64_t ld, in
                                out_in_box, out_in_box_any, face_sel ? out_sel_open : nullptr,
                                face_sel ? out_sel_open_any : nullptr, out_worst};
   const int rc = ccmpc::launch_face_audit(a, ccmpc::as_stream(stream));
+  CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
+  CCMPC_LAUNCH_CHECK();
+  return CCMPC_OK;
+}
+
+// ---- Monte-Carlo calibration of the box-face rows (face_quantile.hip) ------------------------
+extern "C" size_t ccmpc_face_quantile_workspace_bytes(int64_t T, int64_t n_cells) {
+  if (T < 1 || T > ccmpc::kAuditMaxT || n_cells < 0 || n_cells >= (1 << 30)) return 0;
+  return ccmpc::face_quantile_workspace_bytes(T, n_cells);
+}
+
+extern "C" int ccmpc_face_quantile(const void *positions, int dtype, int64_t ld, int64_t T,
+                                   const double *origin, const int64_t *cell_off,
+                                   const int64_t *cell_cnt, int64_t n_cells,
+                                   int64_t n_particles_bound, const double *past_last,
+                                   const double *extent, double car_r, const double *plan,
+                                   int64_t ld_plan, const int32_t *cell_plan,
+                                   const int64_t *cell_allow, double margin, void *workspace,
+                                   size_t workspace_bytes, double *out_q, int64_t *out_arg,
+                                   ccmpc_gather_rec *out_cut, int32_t *out_status,
+                                   ccmpc_stream_t stream) {
+  static_assert(sizeof(ccmpc_gather_rec) == 32, "ccmpc_gather_rec is 32 bytes");
+  CCMPC_REQUIRE(T >= 1 && T <= ccmpc::kAuditMaxT, "T must be in [1, 40]");
+  CCMPC_REQUIRE(std::isfinite(car_r), "car_r must be finite");
+  CCMPC_REQUIRE(std::isfinite(margin) && margin >= 0.0, "margin must be finite and >= 0");
+  CCMPC_REQUIRE(ld_plan >= 2, "ld_plan must be >= 2");
+  CCMPC_REQUIRE(n_cells >= 0 && n_cells < (1 << 30), "bad n_cells");
+  CCMPC_REQUIRE(n_particles_bound >= 0 && n_particles_bound < (int64_t(1) << 32),
+                "n_particles_bound must be in [0, 2^32)");
+  CCMPC_REQUIRE(dtype == CCMPC_F64 || dtype == CCMPC_F32, "bad dtype");
+  CCMPC_REQUIRE(ld % 4 == 0 && ld > 0, "ld must be a positive multiple of 4");
+  CCMPC_REQUIRE(positions && cell_off && cell_cnt && past_last && extent && plan, "null pointer");
+  CCMPC_REQUIRE(out_q && out_arg && out_cut && out_status, "null output");
+  CCMPC_REQUIRE(ccmpc::aligned(positions, 16), "positions must be 16-byte aligned");
+  CCMPC_REQUIRE(ccmpc::aligned(plan, 8) && ccmpc::aligned(past_last, 8) &&
+                    ccmpc::aligned(extent, 8) && ccmpc::aligned(cell_allow, 8),
+                "plan, past_last, extent and cell_allow must be 8-byte aligned");
+  CCMPC_REQUIRE(ccmpc::aligned(out_q, 8) && ccmpc::aligned(out_arg, 8) &&
+                    ccmpc::aligned(out_cut, 16) && ccmpc::aligned(out_status, 4),
+                "outputs must be 8-byte (out_cut 16-byte, out_status 4-byte) aligned");
+  if (workspace_bytes < ccmpc::face_quantile_workspace_bytes(T, n_cells)) {
+    ccmpc::set_error("ccmpc_face_quantile: workspace too small");
+    return CCMPC_ERR_ARG;
+  }
+  if (n_cells == 0) return CCMPC_OK;
+  CCMPC_REQUIRE(workspace && ccmpc::aligned(workspace, 16),
+                "workspace must be non-null and 16-byte aligned");
+  const size_t R = static_cast<size_t>(n_cells) * static_cast<size_t>(T) * 4;
+  unsigned char *ws = static_cast<unsigned char *>(workspace);
+  ccmpc::FaceQuantArgs a{};
+  a.pos = positions;
+  a.dtype = dtype;
+  a.ld = ld;
+  a.T = static_cast<int>(T);
+  a.origin = origin;
+  a.off = cell_off;
+  a.cnt = cell_cnt;
+  a.n_cells = static_cast<int>(n_cells);
+  a.n_bound = n_particles_bound;
+  a.past_last = past_last;
+  a.extent = extent;
+  a.car_r = car_r;
+  a.plan = plan;
+  a.ld_plan = ld_plan;
+  a.cell_plan = cell_plan;
+  a.allow = cell_allow;
+  a.margin = margin;
+  a.bins = reinterpret_cast<uint32_t *>(ws);
+  a.prefix = reinterpret_cast<uint64_t *>(ws + R * 1024);
+  a.rank = reinterpret_cast<int64_t *>(ws + R * (1024 + 8));
+  a.arg = reinterpret_cast<uint32_t *>(ws + R * (1024 + 16));
+  a.state = reinterpret_cast<int32_t *>(ws + R * (1024 + 20));
+  a.out_q = out_q;
+  a.out_arg = out_arg;
+  a.out_cut = reinterpret_cast<double2 *>(out_cut);
+  a.out_status = out_status;
+  const int rc = ccmpc::launch_face_quantile(a, ccmpc::as_stream(stream));
   CCMPC_REQUIRE(rc == CCMPC_OK, "too many work items for one grid");
   CCMPC_LAUNCH_CHECK();
   return CCMPC_OK;

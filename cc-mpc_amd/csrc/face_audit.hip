@@ -16,7 +16,8 @@
 //    selected row at any step" bits are registers: one wave mask per particle slot, kept in
 //    scalar registers and updated with scalar instructions from the step's ballots.
 //  * The heading is faces.hpp's face_heading, the one ccmpc_face_constraints forms: bit for bit
-//    the unit vector the records' coefficients were built from.
+//    the unit vector the records' coefficients were built from.  The four face values come from
+//    face_values (face_audit.hpp), the inline function face_quantile.hip evaluates too.
 //  * Once per workgroup the cell's plan row (2T doubles) and face_sel row (T ints) are staged in
 //    LDS.
 //  * Counts are wave ballots + population counts; lanes 0..4 of a wave add the step's five
@@ -205,11 +206,8 @@ __global__ __launch_bounds__(kFaceAuditThreads) void face_audit_kernel(FaceAudit
       const double x = face_world(b[0][j], o0), y = face_world(b[1][j], o1);
       const double xp = t == 0 ? past_x : face_world(pb[0][j], o0);
       const double yp = t == 0 ? past_y : face_world(pb[1][j], o1);
-      double S, C;
-      face_heading(x - xp, y - yp, S, C);
-      const double ex = X - x, ey = Y - y;
-      const double p = C * ex - S * ey, q = S * ex + C * ey;
-      const double v0 = hlat - p, v1 = hlon - q, v2 = hlat + p, v3 = hlon + q;
+      double S, C, v0, v1, v2, v3;
+      face_values(x, y, xp, yp, X, Y, hlat, hlon, S, C, v0, v1, v2, v3);
       const unsigned long long b0 = __ballot(v0 > 0.0) & vmask[j], b1 = __ballot(v1 > 0.0) & vmask[j],
                                b2 = __ballot(v2 > 0.0) & vmask[j], b3 = __ballot(v3 > 0.0) & vmask[j];
       const unsigned long long in = b0 & b1 & b2 & b3;

@@ -3,8 +3,27 @@
 // argument checks is ccmpc_face_audit in capi.hip.
 #pragma once
 #include "audit.hpp"
+#include "faces.hpp"
 
 namespace ccmpc {
+
+// The four face values of one particle at one step, as ccmpc_face_audit's contract states them
+// (include/ccmpc.h): (x, y) the particle's world position, (xp, yp) its previous one (past_last
+// at step 0), (X, Y) the plan point.  Float64, no contraction, products before sums.  S, C: the
+// heading's sine and cosine (face_heading).  Shared by face_audit.hip and face_quantile.hip, so
+// both form the same bits.
+__device__ __forceinline__ void face_values(double x, double y, double xp, double yp, double X,
+                                            double Y, double hlat, double hlon, double &S,
+                                            double &C, double &v0, double &v1, double &v2,
+                                            double &v3) {
+  face_heading(x - xp, y - yp, S, C);
+  const double ex = X - x, ey = Y - y;
+  const double p = C * ex - S * ey, q = S * ex + C * ey;
+  v0 = hlat - p;
+  v1 = hlon - q;
+  v2 = hlat + p;
+  v3 = hlon + q;
+}
 
 struct FaceAuditArgs {
   const void *pos;

@@ -971,6 +971,79 @@ int ccmpc_face_cuts(const ccmpc_face_rec *rec, int64_t T, int64_t n_scenes,
                     double *out_viol, int32_t *out_state, ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Monte-Carlo calibration of the box-face rows to a risk budget: by how far does face f's row
+ * of (cell, t) miss, or clear, a budget of cell_allow[c] open particles at a plan -- and which
+ * half-space would meet it?  The companion of ccmpc_face_audit (which counts) as
+ * ccmpc_risk_quantile is of ccmpc_risk_audit; no reference counterpart.  An exact order
+ * statistic of ccmpc_face_audit's face values on the particle store.
+ *
+ * Store arguments (positions .. n_particles_bound), past_last, extent, car_r, plan, ld_plan and
+ * cell_plan are exactly those of ccmpc_face_audit, with the same F32 rule.
+ *  cell_allow[c]   device int64, NULL = all zeros: the number m of particles of cell c a row
+ *                  may leave open (as ccmpc_risk_quantile)
+ *  margin          >= 0 and finite: subtracted from every cut's rhs (below)
+ *
+ * The values v_f, f = 0..3, of every particle of (cell, t) are ccmpc_face_audit's, word for
+ * word: ex, ey, p, q, hlat, hlon, v0..v3 in float64 with no contraction, products before sums,
+ * the heading as ccmpc_face_constraints forms it.  Both calls evaluate one shared inline
+ * function, so they form the same bits.  N = cell_cnt[c], m = cell_allow[c].
+ *
+ * Outputs, all written in full by every call (neither they nor the workspace need initial
+ * values):
+ *  out_q[c][T][4]     double.  m < N: the (m+1)-th largest v_f + 0.0 over the cell's particles
+ *                     at step t, i.e. index N-1-m of the ascending sort by the order-preserving
+ *                     key (the + 0.0 makes -0 a +0, so bit order equals value order).  It is the
+ *                     distance in metres along face f's normal by which the row misses (> 0) or
+ *                     clears (<= 0) the budget at this plan: #{v_f > q} <= m by construction, so
+ *                     out_face_open[c][t][f] <= m  <=>  q <= 0.  With m = 0 it is out_worst.
+ *  out_arg[c][T][4]   int64: the index within the cell of the particle that attains q; among
+ *                     particles whose value has q's bits, the lowest index.  -1 where nothing is
+ *                     selected.
+ *  out_cut[c][T][4]   ccmpc_gather_rec: the half-space n . x <= rhs on which that particle's own
+ *                     face inequality v_f(x) <= 0 holds, shifted to the budget.  n is the gradient
+ *                     of v_f in (X, Y): (-c, s), (-s, -c), (c, -s), (s, c) for f = 0..3, (c, s)
+ *                     the arg particle's heading (the same bits the selection used).  With
+ *                     P = (X, Y) the plan point of (c, t), in this order:
+ *                       rhs = ((n0*X + n1*Y) - q) - margin
+ *                     so n . P - rhs = q + margin up to rounding.  side = -1, t_tau = t, status
+ *                     0, as ccmpc_face_cuts writes its cuts.  The record is empty (status
+ *                     CCMPC_CUT_EMPTY, n = rhs = 0) where q + margin <= 0 (the row already meets
+ *                     the budget) or nothing is selected; ccmpc_mpc_qp skips empty records.
+ *                     Where all particles of the cell share a heading, v_f is one affine
+ *                     function of the plan point shifted per particle, q is affine in the plan
+ *                     and the cut is exact; with differing headings {x : q(x) <= 0} is not convex
+ *                     in general and the cut is the selected particle's constraint only.
+ *  out_status[c][T]   int32.  0: a value was selected.  CCMPC_CAL_VACUOUS: m >= N, empty cells
+ *                     included: q = -inf, arg = -1, empty cuts.  CCMPC_CAL_SKIPPED: m < 0,
+ *                     detected on the device: q = NaN, arg = -1, empty cuts.
+ *
+ * Workspace: ccmpc_face_quantile_workspace_bytes(T, n_cells) bytes (0 for arguments the call
+ * rejects), 16-byte aligned: 1048 bytes per (cell, t, face), never a function of the particle
+ * count.  Do not share one workspace between concurrent streams.
+ * Launches, fixed by (T, n_cells, n_particles_bound): the initial values; 8 x (a counting pass
+ * over the store, a narrowing launch) -- ccmpc_risk_quantile's radix select on the 64-bit key, 8
+ * bits per pass, on ccmpc_face_audit's streaming geometry, in chunks of 8 steps x 4 faces; one
+ * more pass that finds the lowest index holding q's bits; the cuts.  Every pass forms the
+ * headings again.  Integer atomics only (32-bit adds and minima): no output bit depends on
+ * execution order.  No host synchronisation, no host read of device memory: capturable.
+ *
+ * CCMPC_ERR_ARG, all checked on the host before any launch: those of ccmpc_face_audit (T outside
+ * [1, 40], ld not a positive multiple of 4, ld_plan < 2, car_r not finite, n_cells < 0, a NULL
+ * positions, cell_off, cell_cnt, past_last, extent, plan or output), margin negative or not
+ * finite, a workspace that is too small, NULL (n_cells > 0) or not 16-byte aligned,
+ * n_particles_bound >= 2^32 (counts and indices are 32-bit).  Positions are assumed finite;
+ * non-finite ones give unspecified values but no out-of-range access.
+ * ------------------------------------------------------------------------------------- */
+size_t ccmpc_face_quantile_workspace_bytes(int64_t T, int64_t n_cells);
+int ccmpc_face_quantile(const void *positions, int dtype, int64_t ld, int64_t T,
+                        const double *origin, const int64_t *cell_off, const int64_t *cell_cnt,
+                        int64_t n_cells, int64_t n_particles_bound, const double *past_last,
+                        const double *extent, double car_r, const double *plan, int64_t ld_plan,
+                        const int32_t *cell_plan, const int64_t *cell_allow, double margin,
+                        void *workspace, size_t workspace_bytes, double *out_q, int64_t *out_arg,
+                        ccmpc_gather_rec *out_cut, int32_t *out_status, ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * TEST ONLY (not a reference interface): the half-space tail's device functions -- the ones
  * ccmpc_minkowski_cycle / ccmpc_minkowski / ccmpc_affine_scale run per record -- on n batched
  * inputs, so the reference's component golden vectors reach the device arithmetic.  Device
