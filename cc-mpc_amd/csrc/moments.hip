@@ -32,9 +32,24 @@
 
 // CCMPC_PROBE & 4 (diagnostic build only): per-workgroup phase timestamps (s_memrealtime,
 // 100 MHz) into a device table read back by ccmpc_probe_timestamps.
+// In a table of its own (every slot is taken): the time the workgroup's LAST wave left its stream
+// loop -- slot 2 is wave 0's, and the combine's barrier waits for the slowest.  The waves meet in
+// an LDS word (a global atomic would be waited for in the combine and show up there); thread 0
+// zeroes it at slot 0, a microsecond before any wave is through its stream, and writes it out at
+// slot 3, behind the combine's barriers.  Read back by ccmpc_probe_stream_end.
 #if CCMPC_PROBE & 4
 constexpr int kProbeSlots = 8, kProbeMaxWG = 8192;
 __device__ unsigned long long g_probe_ts[kProbeMaxWG * kProbeSlots];
+__device__ unsigned long long g_probe_stream_end[kProbeMaxWG];
+__device__ __forceinline__ unsigned long long &probe_stream_end_lds() {
+  __shared__ unsigned long long t;
+  return t;
+}
+#define PROBE_STREAM_END()                                                                     \
+  do {                                                                                         \
+    if ((threadIdx.x & 63) == 0)                                                               \
+      atomicMax(&probe_stream_end_lds(), __builtin_amdgcn_s_memrealtime());                    \
+  } while (0)
 #define PROBE_TS(k)                                                                            \
   do {                                                                                         \
     if (threadIdx.x == 0 && blockIdx.x < kProbeMaxWG)                                          \
@@ -43,10 +58,16 @@ __device__ unsigned long long g_probe_ts[kProbeMaxWG * kProbeSlots];
       g_probe_ts[blockIdx.x * kProbeSlots + 7] =                                               \
           (static_cast<unsigned long long>(__builtin_amdgcn_s_getreg(0xF814)) << 32) |         \
           __builtin_amdgcn_s_getreg(0xF804); /* XCC_ID : HW_ID, slot 7 */                       \
+    if ((k) == 0 && threadIdx.x == 0) probe_stream_end_lds() = 0;                              \
+    if ((k) == 3 && threadIdx.x == 0 && blockIdx.x < kProbeMaxWG)                              \
+      g_probe_stream_end[blockIdx.x] = probe_stream_end_lds();                                 \
   } while (0)
 #else
 #define PROBE_TS(k) \
   do {              \
+  } while (0)
+#define PROBE_STREAM_END() \
+  do {                     \
   } while (0)
 #endif
 // CCMPC_PROBE & 16 (with 4): slot 7 = the root gather's end instead of the hardware ids
@@ -206,6 +227,33 @@ __device__ __forceinline__ void load_group(typename LaneVec<P, W>::type (&v)[S][
   }
 }
 
+// CCMPC_SUBSTEP_FENCE: a scheduling fence between a group's sub-steps (S > 1: RB = 1 and 2; at
+// RB >= 3 a group is one sub-step).  Without it the scheduler hoists every sub-step's shift and
+// mask, and with them the wait for that sub-step's loads, above the MFMAs: one MFMA issued behind
+// the first wait and the other 4 S - 1 behind the last, so a wave's matrix-core time began when
+// its LAST load had landed.  With it sub-step s issues its W MFMAs per tile when its own loads
+// are in, ahead of sub-step s + 1's wait.  The MFMAs keep their order and chains, s1 its
+// expression: the same bits.  The fence alone holds the machine scheduler only: the widening, the
+// shift and the mask are pure arithmetic, which the optimiser moves above a fence as it likes (it
+// did, in the remainder after the ring loop), so each sub-step also names its loaded registers in
+// an empty asm behind its fence -- their first use, and the wait it carries, then cannot start
+// above it.
+#ifndef CCMPC_SUBSTEP_FENCE
+#define CCMPC_SUBSTEP_FENCE 1
+#endif
+__device__ __forceinline__ void pin_loaded(Quad<double> &q) {
+  ccmpc_d2v lo = {q.lo.x, q.lo.y}, hi = {q.hi.x, q.hi.y};
+  asm volatile("" : "+v"(lo), "+v"(hi));
+  q.lo = make_double2(lo.x, lo.y);
+  q.hi = make_double2(hi.x, hi.y);
+}
+__device__ __forceinline__ void pin_loaded(Quad<float> &q) {
+  ccmpc_f4v t = {q.v.x, q.v.y, q.v.z, q.v.w};
+  asm volatile("" : "+v"(t));
+  q.v = make_float4(t.x, t.y, t.z, t.w);
+}
+template <typename P>
+__device__ __forceinline__ void pin_loaded(Pair<P> &) {}  // W = 2: one sub-step per group
 template <typename P, int RB, int S, int NACC, int W>
 __device__ __forceinline__ void mfma_group(const typename LaneVec<P, W>::type (&raw)[S][RB],
                                            const double (&sh)[RB], const bool (&live)[RB],
@@ -214,17 +262,27 @@ __device__ __forceinline__ void mfma_group(const typename LaneVec<P, W>::type (&
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     const int64_t q = gbase + 4 * W * s + W * g;
+    typename LaneVec<P, W>::type x[RB];
+#pragma unroll
+    for (int b = 0; b < RB; ++b) x[b] = raw[s][b];
+#if CCMPC_SUBSTEP_FENCE
+    if (S > 1) {
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int b = 0; b < RB; ++b) pin_loaded(x[b]);
+    }
+#endif
     double v[RB][W];
 #pragma unroll
     for (int b = 0; b < RB; ++b)
 #pragma unroll
       for (int j = 0; j < W; ++j)  // shifted; out-of-range slots and dead rows become 0
 #if CCMPC_PROBE & 32  // diagnostic build only: no masks (wrong at partial groups; timing bound)
-        v[b][j] = raw[s][b][j] - sh[b];
+        v[b][j] = x[b][j] - sh[b];
 #elif CCMPC_PROBE & 64  // diagnostic build only: neither masks nor the shift
-        v[b][j] = raw[s][b][j];
+        v[b][j] = x[b][j];
 #else
-        v[b][j] = (live[b] && q + j < p1) ? raw[s][b][j] - sh[b] : 0.0;
+        v[b][j] = (live[b] && q + j < p1) ? x[b][j] - sh[b] : 0.0;
 #endif
 #pragma unroll
     for (int j = 0; j < W; ++j) {
@@ -337,16 +395,45 @@ __device__ __forceinline__ WaveRange wave_range(int64_t a, int64_t b, int w, int
   return r;
 }
 
-// The per-cell inputs of the half-space tail: issued at an item's start, landing behind its
-// stream loop (thread i < 2T: ref_traj row, then the 3 risk constants).  (The two guarded loads
-// share a result register, so the compiler waits for the first before it issues the second --
-// a vmcnt(0) in wave 0 ahead of its particle loads.  One load from a selected address removes
-// that wait and was measured: no gain, bench step 8.84 against 8.83 us, profiles/r11.)
+// The per-cell inputs of the half-space tail (thread i < 2T: ref_traj row, then the 3 risk
+// constants), landing behind the item's stream loop and first used at the ref_lds write after it.
+// CCMPC_TAIL_LATE: issued BEHIND the item's first load group(s), as one load from a selected
+// address.  Issued at the item's start, as two guarded loads, it put two waits in front of wave
+// 0's particle loads that waves 1-3 (who skip it) do not take and then sit out at the combine's
+// barrier: the lgkmcnt(0) for mp's pointers, which also covers the argument loads the compiler
+// places behind locate (scalar loads return out of order, so any wait is for all of them: cold
+// lines of a fresh argument slot), and a vmcnt(0) at the join of two loads into one register.
+// Vector loads return in order, so behind the particle loads it is in no MFMA wait's way.  (The
+// selected-address form alone, at the item's start, was measured in r11: no gain.)
+#ifndef CCMPC_TAIL_LATE
+#define CCMPC_TAIL_LATE 1
+#endif
 __device__ __forceinline__ double prefetch_tail(const MinkParams &mp, const ItemLoc &loc,
                                                 int rows) {
+#if CCMPC_TAIL_LATE
+  // branch-free, like the particle loads: every thread loads, threads past 2T + 2 re-read the
+  // last constant (their value is never stored)
+  const int i = min(static_cast<int>(threadIdx.x), rows + 2);
+  const bool ref = i < rows;
+  const double *base = ref ? mp.ref_traj : mp.cell_risk;
+  const int64_t at =
+      ref ? static_cast<int64_t>(loc.ref_sel) * rows + i : int64_t(3 * loc.cell + (i - rows));
+  return base[at];
+#else
   if (threadIdx.x < rows) return mp.ref_traj[static_cast<int64_t>(loc.ref_sel) * rows + threadIdx.x];
   if (threadIdx.x < rows + 3) return mp.cell_risk[3 * loc.cell + (threadIdx.x - rows)];
   return 0.0;
+#endif
+}
+// The same for a wave with no particles, waited for at once: the wait counter's bookkeeping is
+// per register and joins paths pessimistically, so a load left in flight here would put a wait
+// for everything older than the particle loads in front of the load above (same register).
+__device__ __forceinline__ double prefetch_tail_landed(const MinkParams &mp, const ItemLoc &loc,
+                                                       int rows) {
+  const double v = prefetch_tail(mp, loc, rows);
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+  return v;
 }
 
 // TC, the compile-time horizon (the NTH pattern: 0 = the run-time T, 8 = T is 8, which launch()
@@ -411,7 +498,7 @@ void moments_kernel(
     const int r = lane & 15;
     const int g = lane >> 4;
     const int64_t cnt = loc.cnt;
-    const double pre = MINK ? prefetch_tail(mp, loc, rows) : 0.0;
+    double pre = (MINK && !CCMPC_TAIL_LATE) ? prefetch_tail(mp, loc, rows) : 0.0;
     // a whole-cell item longer than a chunk deals its load groups round-robin, as balanced
     // items do, so every wave streams ~1/NW of the cell
     const bool rr = BAL || (b - a > (int64_t(1) << lg_chunk));
@@ -455,6 +542,10 @@ void moments_kernel(
       // while one is multiplied
 #pragma unroll
       for (int d = 0; d < DP - 1; ++d) load_group<P, RB, S, W>(buf[d], rowp, wr.p0 + d * st, p1, g);
+      if (MINK && CCMPC_TAIL_LATE) {  // the fence keeps its address and its scalar wait down here
+        __builtin_amdgcn_sched_barrier(0);
+        pre = prefetch_tail(mp, loc, rows);
+      }
       int64_t gi = 0;
       for (; gi + DP <= ngroups; gi += DP) {
         if (BAL) progress_prio(gi, ngroups);
@@ -471,8 +562,11 @@ void moments_kernel(
       for (int d = 0; d < DP - 1; ++d)  // the < DP groups left were loaded ahead
         if (gi + d < ngroups)
           mfma_group<P, RB, S, NACC, W>(buf[d], sh, live, wr.p0 + (gi + d) * st, p1, g, acc, s1);
+    } else if (MINK && CCMPC_TAIL_LATE) {
+      pre = prefetch_tail_landed(mp, loc, rows);  // a wave with no particles
     }
     PROBE_TS(2);
+    PROBE_STREAM_END();
 #if CCMPC_PRIO || CCMPC_PROGRESS_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
@@ -690,7 +784,7 @@ __global__ __launch_bounds__(kThreads4, m4_occ<P>(NB)) void moments4_kernel(
 #endif
     const int paddr = 4 * (16 * c + m);        // matrix lane (c, m) <- loading lane 16 c + m
     const int64_t cnt = loc.cnt;
-    const double pre = MINK ? prefetch_tail(mp, loc, rows) : 0.0;
+    double pre = (MINK && !CCMPC_TAIL_LATE) ? prefetch_tail(mp, loc, rows) : 0.0;
     const WaveRange wr = wave_range<BAL>(a, b, w, kNW4, int64_t(1) << lg_wq, 16 * Row4<P>::W);
     const int64_t p1 = wr.p1;
 
@@ -718,6 +812,10 @@ __global__ __launch_bounds__(kThreads4, m4_occ<P>(NB)) void moments4_kernel(
     if (ngroups > 0) {
 #pragma unroll
       for (int d = 0; d < DP - 1; ++d) load_group4<P, NB>(buf[d], rowp, wr.p0 + d * st, p1, ml);
+      if (MINK && CCMPC_TAIL_LATE) {  // as in moments_kernel
+        __builtin_amdgcn_sched_barrier(0);
+        pre = prefetch_tail(mp, loc, rows);
+      }
       int64_t gi = 0;
       for (; gi + DP <= ngroups; gi += DP) {
         if (BAL) progress_prio(gi, ngroups);
@@ -733,8 +831,11 @@ __global__ __launch_bounds__(kThreads4, m4_occ<P>(NB)) void moments4_kernel(
       for (int d = 0; d < DP - 1; ++d)
         if (gi + d < ngroups)
           mfma_group4<P, NB>(buf[d], sh, live, wr.p0 + (gi + d) * st, p1, m, paddr, acc, s1);
+    } else if (MINK && CCMPC_TAIL_LATE) {
+      pre = prefetch_tail_landed(mp, loc, rows);
     }
     PROBE_TS(2);
+    PROBE_STREAM_END();
 #if CCMPC_PROGRESS_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
@@ -1076,9 +1177,17 @@ extern "C" int ccmpc_probe_timestamps(void *host, int reset) {
   const size_t bytes = sizeof(g_probe_ts);
   if (reset) {
     static unsigned long long zeros[kProbeMaxWG * kProbeSlots];
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_probe_ts), zeros, bytes) == hipSuccess ? 0 : -1;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_probe_ts), zeros, bytes) == hipSuccess &&
+                   hipMemcpyToSymbol(HIP_SYMBOL(g_probe_stream_end), zeros,
+                                     sizeof(g_probe_stream_end)) == hipSuccess
+               ? 0 : -1;
   }
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_probe_ts), bytes) == hipSuccess ? 0 : -1;
+}
+// host[kProbeMaxWG]: when each workgroup's last wave left its stream loop (reset with the table)
+extern "C" int ccmpc_probe_stream_end(void *host) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_probe_stream_end),
+                             sizeof(g_probe_stream_end)) == hipSuccess ? 0 : -1;
 }
 #endif
 

@@ -3,6 +3,8 @@ libccmpc.so copied over the real one; see tools/probe_variants.sh).
 
 Slots (s_memrealtime, 100 MHz): 0 start, 1 located, 2 wave 0's stream loop done,
 3 combined + published, 4 tree climbed (or gave up), 5 finalised, 6 half-spaces done.
+A library that has ccmpc_probe_stream_end also gives the time the workgroup's LAST wave left its
+stream loop ("wg loop end / dur": what the combine's barrier waits for; slot 2 is wave 0's).
 """
 import ctypes
 import os
@@ -44,6 +46,11 @@ def one(name, what, dev, lib, back_to_back=1):
     live = ts[:, 0] > 0
     wg = np.flatnonzero(live)
     ts = ts[live]
+    wg_end = None
+    if hasattr(lib, "ccmpc_probe_stream_end"):
+        ebuf = np.zeros(MAXWG, np.uint64)
+        assert lib.ccmpc_probe_stream_end(ebuf.ctypes.data_as(ctypes.c_void_p)) == 0
+        wg_end = ebuf.astype(np.int64)[live]
     t0 = ts[:, 0].min()
     rel = np.where(ts > 0, ts - t0, -1)
     end = rel[:, :7].max()
@@ -54,6 +61,10 @@ def one(name, what, dev, lib, back_to_back=1):
     print("  locate     ", stats(rel[:, 1] - rel[:, 0]))
     print("  loop end   ", stats(rel[:, 2]))
     print("  loop dur   ", stats(rel[:, 2] - rel[:, 1]))
+    if wg_end is not None:
+        ok = wg_end > 0
+        print("  wg loop end", stats((wg_end - t0)[ok]))
+        print("  wg loop dur", stats((wg_end - t0 - rel[:, 1])[ok]))
     print("  combine    ", stats(rel[:, 3] - rel[:, 2]))
     print("  climb(non) ", stats((rel[:, 4] - rel[:, 3])[~fin]))
     print("  climb(last)", stats((rel[:, 4] - rel[:, 3])[fin]))
@@ -81,6 +92,9 @@ def main():
     lib = _lib.load()
     lib.ccmpc_probe_timestamps.restype = ctypes.c_int
     lib.ccmpc_probe_timestamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    if hasattr(lib, "ccmpc_probe_stream_end"):
+        lib.ccmpc_probe_stream_end.restype = ctypes.c_int
+        lib.ccmpc_probe_stream_end.argtypes = [ctypes.c_void_p]
     jobs = [a.split(":") for a in sys.argv[1:]] or (
         [(n, "moments") for n in CONFIGS] + [("C2", "cycle")])
     for _ in range(int(os.environ.get("REPS", "1"))):  # REPS=n: n tables, to see their scatter
