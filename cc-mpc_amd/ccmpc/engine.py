@@ -743,6 +743,131 @@ def _audit_rows(rec_kind, T):
     return T * (T - 1) // 2 if half else T
 
 
+def _audit_plan_arg(plan, cell_plan, C, T, dev):
+    """risk_audit's checks of plan / cell_plan: (plan as a contiguous (n, T, 2) float64 device
+    tensor, cell_plan as an int32 device tensor or None)."""
+    t_plan = torch.as_tensor(plan, device=dev)
+    if t_plan.dim() == 2:
+        t_plan = t_plan.unsqueeze(0)
+    if t_plan.dim() != 3 or t_plan.shape[1] < T or t_plan.shape[2] < 2:
+        raise ValueError(f"plan must be (T, >= 2) or (n_plans, T, >= 2) with T >= {T}")
+    if (t_plan.dtype != torch.float64 or tuple(t_plan.shape[1:]) != (T, 2)
+            or not t_plan.is_contiguous()):
+        t_plan = t_plan[:, :T, :2].to(torch.float64).contiguous()
+    n_plans = int(t_plan.shape[0])
+    if cell_plan is None:
+        if n_plans != 1:
+            raise ValueError(f"{n_plans} plans need cell_plan")
+    elif torch.is_tensor(cell_plan):    # device-resident: its range is the caller's contract
+        if (cell_plan.dtype != torch.int32 or tuple(cell_plan.shape) != (C,)
+                or cell_plan.device != dev or not cell_plan.is_contiguous()):
+            raise ValueError(f"cell_plan must be a contiguous int32 [{C}] tensor on {dev}")
+    else:
+        host = np.asarray(cell_plan, np.int64).reshape(-1)
+        if host.shape[0] != C or (C and (host.min() < 0 or host.max() >= n_plans)):
+            raise ValueError(f"cell_plan must hold {C} indices in [0, {n_plans})")
+        cell_plan = torch.as_tensor(host.astype(np.int32), device=dev)
+    return t_plan, cell_plan
+
+
+def _audit_rec_arg(rec, rec_kind, C, T):
+    """risk_audit's checks of rec / rec_kind: (rows per cell P, rec as contiguous (C, P, width)
+    bytes)."""
+    if rec_kind not in (_lib.REC_KIND_HALFSPACE, _lib.REC_KIND_AFFINE,
+                        _lib.REC_KIND_HALFSPACE_COMPACT, _lib.REC_KIND_AFFINE_COMPACT):
+        raise ValueError(f"unknown rec_kind {rec_kind!r}")
+    P = _audit_rows(rec_kind, T)
+    width = 32 if rec_kind >= _lib.REC_KIND_HALFSPACE_COMPACT else 128
+    if rec.dtype != torch.uint8:
+        rec = rec.view(torch.uint8)
+    rec = rec.reshape(C, -1, width) if rec.dim() != 3 else rec
+    if rec.shape[0] != C or rec.shape[2] != width or rec.shape[1] < P:
+        raise ValueError(f"rec must be ({C}, >= {P}, {width}) bytes for rec_kind {rec_kind}")
+    if P == 0:
+        pass                        # T = 1 half-space kinds: no rows, only out_open
+    elif rec.shape[1] != P:         # rows of a longer horizon's buffer
+        rec = rec[:, :P].contiguous()
+    elif not rec.is_contiguous():
+        rec = rec.contiguous()
+    return P, rec
+
+
+def _audit_out(out, on_p, on_r, C, T, P, dev):
+    """A fresh RiskAudit, or `out` with the shapes of its enabled halves checked."""
+    if out is None:
+        i64 = dict(dtype=torch.int64, device=dev)
+        return RiskAudit(
+            torch.empty((C, T), **i64) if on_p else None,
+            torch.empty((C,), **i64) if on_p else None,
+            torch.empty((C, T), dtype=torch.float64, device=dev) if on_p else None,
+            torch.empty((C, P), **i64) if on_r else None,
+            torch.empty((C, T), **i64) if on_r else None)
+    want = dict(hit=(C, T), hit_any=(C,), min_d2=(C, T), rec_open=(C, P), open=(C, T))
+    for name, shape in want.items():
+        t = getattr(out, name)
+        on = on_p if name in ("hit", "hit_any", "min_d2") else on_r
+        if on and (t is None or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"out.{name} must be a contiguous {shape} tensor")
+    return out
+
+
+def ideal_risk_audit(prev_mean, prev_cov, src_cell, T, n_samples, plan=None, rec=None,
+                     rec_kind=None, R=risk.R_COLLISION, cell_plan=None, x0=None, seed=0,
+                     seed_dev=None, rng_cell=None, out=None):
+    """risk_audit on the samples of the ideal rollout, which are never materialised
+    (ccmpc_ideal_risk_audit): the outputs equal ideal_rollout(prev_mean, prev_cov, src_cell, T,
+    n_samples, x0=x0, seed=seed, rng_cell=rng_cell) followed by risk_audit on that store, count
+    for count and min_d2 bit for bit, at no HBM traffic for the samples.
+
+    Rollout arguments as ideal_minkowski_cycle (src_cell / rng_cell int32 device tensors [C],
+    x0 [C, 2] float64 or None); seed_dev: a uint64-sized device tensor that overrides seed, so
+    a captured call audits a fresh seed per replay.  plan / cell_plan / rec / rec_kind / R / out
+    as risk_audit, with n_samples particles in every cell.
+    Returns (RiskAudit, status): status [C] int32 is the rollout's.  out: a previous call's
+    (RiskAudit, status) pair, or a bare RiskAudit (the status is then not written and returned
+    as None); nothing is allocated then, so the call can be captured.  Enqueues two launches on
+    the current stream, never synchronises."""
+    lib = _lib.load()
+    dev = prev_mean.device
+    C = int(src_cell.shape[0])
+    T_src = int(prev_mean.shape[1])
+    T, n_samples = int(T), int(n_samples)
+    if plan is None and rec is None:
+        raise ValueError("ideal_risk_audit needs a plan, records, or both")
+    if not 1 <= T <= T_src - 1:
+        raise ValueError(f"T = {T} outside [1, {T_src - 1}] (the source horizon less one)")
+    t_plan = None
+    if plan is not None:
+        t_plan, cell_plan = _audit_plan_arg(plan, cell_plan, C, T, dev)
+    else:
+        cell_plan = None
+    P = 0
+    if rec is not None:
+        P, rec = _audit_rec_arg(rec, rec_kind, C, T)
+    status = None
+    if out is None:
+        status = torch.empty(C, dtype=torch.int32, device=dev)
+    elif not isinstance(out, RiskAudit):
+        out, status = out
+        if (status.dtype != torch.int32 or tuple(status.shape) != (C,)
+                or not status.is_contiguous()):
+            raise ValueError(f"status must be a contiguous int32 [{C}] tensor")
+    on_p, on_r = plan is not None, rec is not None
+    out = _audit_out(out, on_p, on_r, C, T, P, dev)
+    if C == 0:
+        return out, status
+    _lib.check(lib.ccmpc_ideal_risk_audit(
+        _p(prev_mean), _p(prev_cov), T_src, _p(src_cell), C, T, n_samples, _p(x0),
+        int(seed) & (2**64 - 1), _p(seed_dev), _p(rng_cell), _p(t_plan), _p(cell_plan),
+        # no rows (T = 1 half-space kinds): any non-null address switches the record half on
+        (_p(rec) if P else _p(prev_mean)) if on_r else None, int(rec_kind) if on_r else 0,
+        float(R),
+        _p(out.hit if on_p else None), _p(out.hit_any if on_p else None),
+        _p(out.min_d2 if on_p else None), _p(out.rec_open if on_r else None),
+        _p(out.open if on_r else None), _p(status), _stream()), "ccmpc_ideal_risk_audit")
+    return out, status
+
+
 def risk_audit(store, plan=None, rec=None, rec_kind=None, R=risk.R_COLLISION, cell_plan=None,
                T=None, out=None):
     """Monte-Carlo audit of a plan and / or constraint records on a ParticleStore
@@ -772,62 +897,13 @@ def risk_audit(store, plan=None, rec=None, rec_kind=None, R=risk.R_COLLISION, ce
         raise ValueError("cell offsets must be multiples of 4 particles")
     t_plan = None
     if plan is not None:
-        t_plan = torch.as_tensor(plan, device=dev)
-        if t_plan.dim() == 2:
-            t_plan = t_plan.unsqueeze(0)
-        if t_plan.dim() != 3 or t_plan.shape[1] < T or t_plan.shape[2] < 2:
-            raise ValueError(f"plan must be (T, >= 2) or (n_plans, T, >= 2) with T >= {T}")
-        if (t_plan.dtype != torch.float64 or tuple(t_plan.shape[1:]) != (T, 2)
-                or not t_plan.is_contiguous()):
-            t_plan = t_plan[:, :T, :2].to(torch.float64).contiguous()
-        n_plans = int(t_plan.shape[0])
-        if cell_plan is None:
-            if n_plans != 1:
-                raise ValueError(f"{n_plans} plans need cell_plan")
-        elif torch.is_tensor(cell_plan):    # device-resident: its range is the caller's contract
-            if (cell_plan.dtype != torch.int32 or tuple(cell_plan.shape) != (C,)
-                    or cell_plan.device != dev or not cell_plan.is_contiguous()):
-                raise ValueError(f"cell_plan must be a contiguous int32 [{C}] tensor on {dev}")
-        else:
-            host = np.asarray(cell_plan, np.int64).reshape(-1)
-            if host.shape[0] != C or (C and (host.min() < 0 or host.max() >= n_plans)):
-                raise ValueError(f"cell_plan must hold {C} indices in [0, {n_plans})")
-            cell_plan = torch.as_tensor(host.astype(np.int32), device=dev)
+        t_plan, cell_plan = _audit_plan_arg(plan, cell_plan, C, T, dev)
     else:
         cell_plan = None
     P = 0
     if rec is not None:
-        if rec_kind not in (_lib.REC_KIND_HALFSPACE, _lib.REC_KIND_AFFINE,
-                            _lib.REC_KIND_HALFSPACE_COMPACT, _lib.REC_KIND_AFFINE_COMPACT):
-            raise ValueError(f"unknown rec_kind {rec_kind!r}")
-        P = _audit_rows(rec_kind, T)
-        width = 32 if rec_kind >= _lib.REC_KIND_HALFSPACE_COMPACT else 128
-        if rec.dtype != torch.uint8:
-            rec = rec.view(torch.uint8)
-        rec = rec.reshape(C, -1, width) if rec.dim() != 3 else rec
-        if rec.shape[0] != C or rec.shape[2] != width or rec.shape[1] < P:
-            raise ValueError(f"rec must be ({C}, >= {P}, {width}) bytes for rec_kind {rec_kind}")
-        if P == 0:
-            pass                        # T = 1 half-space kinds: no rows, only out_open
-        elif rec.shape[1] != P:         # rows of a longer horizon's buffer
-            rec = rec[:, :P].contiguous()
-        elif not rec.is_contiguous():
-            rec = rec.contiguous()
-    if out is None:
-        i64 = dict(dtype=torch.int64, device=dev)
-        out = RiskAudit(
-            torch.empty((C, T), **i64) if plan is not None else None,
-            torch.empty((C,), **i64) if plan is not None else None,
-            torch.empty((C, T), dtype=torch.float64, device=dev) if plan is not None else None,
-            torch.empty((C, P), **i64) if rec is not None else None,
-            torch.empty((C, T), **i64) if rec is not None else None)
-    else:
-        want = dict(hit=(C, T), hit_any=(C,), min_d2=(C, T), rec_open=(C, P), open=(C, T))
-        for name, shape in want.items():
-            t = getattr(out, name)
-            on = (plan is not None) if name in ("hit", "hit_any", "min_d2") else (rec is not None)
-            if on and (t is None or tuple(t.shape) != shape or not t.is_contiguous()):
-                raise ValueError(f"out.{name} must be a contiguous {shape} tensor")
+        P, rec = _audit_rec_arg(rec, rec_kind, C, T)
+    out = _audit_out(out, plan is not None, rec is not None, C, T, P, dev)
     on_p, on_r = plan is not None, rec is not None
     if C == 0:
         return out

@@ -621,6 +621,10 @@ class MidlevelAgent:
         self.last_records = None
         self._last_rec = None              # (device records, kind, T) of the last generator
         self._audit_src = None             # (scene, K, T, _last_rec or None) of the last graph step
+        # (prev_mean, prev_cov, src, seed, T, K, _last_rec, scene or None) of the last frame whose
+        # records came from the ideal rollout (audit_ideal_plan); None after any other frame
+        self._ideal_audit_src = None
+        self._ideal_step_inputs = None     # (prev_mean, prev_cov, src, seed) of the last ideal step
         self._face_src = None              # (scene, K, T, face records, gamma, rows) of the last
         #                                    box-face generator (solve_planning_socp's source)
         self._face_audit_src = None        # (past_last [C, 2], extent) of it, for audit_face_rows
@@ -1037,6 +1041,7 @@ class MidlevelAgent:
                                " (the reference fails to load its pickle here)")
             src = self._src_cells(prev[2], K)
             seed = (self.seed * 1_000_003 + int(params.frame)) & (2**63 - 1)
+            ideal = (prev[0], prev[1], src, seed)
             mean, cov, status, rec, pl = engine.ideal_minkowski_cycle(
                 prev[0], prev[1], src, T, self.n_ideal, ref, cr, seed=seed, R=self.R,
                 workspace=self._ws)
@@ -1048,12 +1053,14 @@ class MidlevelAgent:
             mean, cov, rec, pl = engine.minkowski_cycle(scene.store, ref, cr, R=self.R,
                                                         workspace=self._ws)
             m_scene, c_scene = mean, cov
+            ideal = None
         # save_moments (:960): the moments of exactly the particles this step reduced
         self._moments[params.frame] = (mean, cov, list(K), T)
         h = engine.halfspaces(rec)[:, :T * (T - 1) // 2]     # T = 1 keeps one unused slot
         self.last_records = h
         self._last_rec = (rec, mpc.REC_HALFSPACE, T)
         self._audit_src = None
+        self._ideal_audit_src = ideal and ideal + (T, list(K), self._last_rec, None)
         self._last_sbig = False             # the Minkowski rows carry no S_big (:926-939)
         constraints = self._records_to_halfspaces(h, scene, T)
         pl_h = pl.cpu().numpy()
@@ -1085,6 +1092,7 @@ class MidlevelAgent:
         self.last_records = h
         self._last_rec = (rec, mpc.REC_AFFINE, T)
         self._audit_src = None
+        self._ideal_audit_src = None
         self._last_sbig = True              # + S_big_repeated[0, t] on both sides (:1503-1515)
         cons = []
         for c, (o, k) in enumerate(scene.cell_of):
@@ -1170,6 +1178,7 @@ class MidlevelAgent:
         self.last_records = h
         self._last_rec = None
         self._audit_src = None
+        self._ideal_audit_src = None
         self._face_src = None
         self._face_audit_src = None
         mean0 = mean[:, 0, :].cpu().numpy()
@@ -1194,13 +1203,14 @@ class MidlevelAgent:
         cr = self._cell_risk(np.asarray(eps_ura), K)
         ref = self._ref(ref_traj, T)
         m_scene, c_scene = engine.moments(scene.store, workspace=self._ws)
-        tangent = const_idx = None
+        tangent = const_idx = ideal = None
         if T < ph:
             prev = self._saved(params.frame - self.record_interval)
             if prev is None:
                 raise KeyError(f"no moments saved for frame {params.frame - self.record_interval}")
             src = self._src_cells(prev[2], K)
             seed = (self.seed * 1_000_003 + int(params.frame)) & (2**63 - 1)
+            ideal = (prev[0], prev[1], src, seed)
             mean, cov, status = engine.ideal_moments(prev[0], prev[1], src, T, self.n_ideal,
                                                      seed=seed, workspace=self._ws)
             if np.any(status.cpu().numpy() != 0):
@@ -1217,6 +1227,7 @@ class MidlevelAgent:
         self.last_records = h
         self._last_rec = (rec, mpc.REC_AFFINE, T)
         self._audit_src = None
+        self._ideal_audit_src = ideal and ideal + (T, list(K), self._last_rec, None)
         # the scale-ideal rows carry + S_big_repeated[0, t] (:2394-2414), the robust ones
         # do not (:1828-1849)
         self._last_sbig = bool(scaled)
@@ -1296,6 +1307,9 @@ class MidlevelAgent:
         self._last_rec = (g.out.d("rec"), mpc.REC_HALFSPACE, T)
         # audit_plan: the records were generated from the sampled store only at T == ph
         self._audit_src = (scene, list(K), T, self._last_rec if T == ph else None)
+        # audit_ideal_plan: below ph they were generated from the ideal rollout of these inputs
+        self._ideal_audit_src = (None if T == ph else
+                                 self._ideal_step_inputs + (T, list(K), self._last_rec, scene))
         self._last_sbig = False
         return ovs, self._step_tuple(g, o, scene, K, 0, constraints=constraints)
 
@@ -1314,6 +1328,7 @@ class MidlevelAgent:
         self.last_records = h
         self._last_rec = (g.out.d("rec"), mpc.REC_AFFINE, T)
         self._audit_src = (scene, list(K), T, self._last_rec)
+        self._ideal_audit_src = None
         self._last_sbig = True
         st = h["status"]
         if st.any():
@@ -1407,8 +1422,9 @@ class MidlevelAgent:
                      filter_pmf=filter_pmf)
         if kind == "ideal":
             src = self._src_cells_host(prev[2], K)
-            g.set_ideal_inputs(prev[0], prev[1], src,
-                               (self.seed * 1_000_003 + int(params.frame)) & (2**63 - 1))
+            iseed = (self.seed * 1_000_003 + int(params.frame)) & (2**63 - 1)
+            g.set_ideal_inputs(prev[0], prev[1], src, iseed)
+            self._ideal_step_inputs = (prev[0], prev[1], src, iseed)
         if pp:
             g.set_device_inputs(gmm, z_in, eps_in)
         if source == "predictions":
@@ -1612,6 +1628,40 @@ class MidlevelAgent:
         a = engine.risk_audit(scene.store, plan=plan, rec=rec, rec_kind=kind,
                               R=self.R if R is None else float(R), T=T)
         return risk.audit_report(a, scene.store.counts, K, self.prediction_horizon)
+
+    def audit_ideal_plan(self, X_star, R=None):
+        """Monte-Carlo audit of a plan and of the frame's records on the ideal rollout those
+        records were built from (engine.ideal_risk_audit): the counterpart of audit_plan for the
+        shrinking horizon.  Below ph audit_plan counts X_star against the sampled scene, a
+        different distribution from the one the frame's constraints were generated from, and has
+        no record half; here the n_ideal samples of the frame's own rollout (the previous
+        frame's moments, its source cells and the frame's seed) are regenerated on the device,
+        never materialised, and both halves are counted on them.
+        Serves the last frame of the eager Minkowski generator, of the eager affine-tangent
+        generators (affine records) and of predict_and_constrain, each at Tsh < ph; after any
+        other frame it raises RuntimeError.  X_star: (Tsh, >= 2), the QP's X_star; R: default
+        the agent's.  After predict_and_constrain the records live in the step graph's buffers,
+        so they must be audited before the next step of the same shape (raises after it).
+        One eager call; never called implicitly; returns risk.audit_report's dict with every
+        cell's count n_ideal and changes no planner state."""
+        if self._ideal_audit_src is None:
+            raise RuntimeError("the last frame's records were not built from the ideal rollout: "
+                               "call a Minkowski or affine-tangent generator at Tsh < ph first")
+        pm, pc, src, seed, T, K, last, scene = self._ideal_audit_src
+        if scene is not None:
+            scene.check_live()
+        X = np.asarray(X_star, np.float64)
+        if X.ndim != 2 or X.shape[0] != T or X.shape[1] < 2:
+            raise ValueError(f"X_star must be ({T}, >= 2) for the last frame's Tsh = {T}")
+        dev = self.device
+        plan = torch.as_tensor(np.ascontiguousarray(X[None, :, :2]), device=dev)
+        pm = torch.as_tensor(pm, device=dev)
+        pc = torch.as_tensor(pc, device=dev)
+        src = torch.as_tensor(src, dtype=torch.int32, device=dev)
+        a, _ = engine.ideal_risk_audit(pm, pc, src, T, self.n_ideal, plan=plan, rec=last[0],
+                                       rec_kind=last[1], R=self.R if R is None else float(R),
+                                       seed=seed)
+        return risk.audit_report(a, [self.n_ideal] * len(src), K, self.prediction_horizon)
 
     def _face_selection(self, cons, C, T, faces):
         """face_sel [C, T] int32 on the host: -1 for the cells of ungated OVs; for a gated

@@ -709,6 +709,47 @@ int ccmpc_risk_audit(const void *positions, int dtype, int64_t ld, int64_t T,
                      int64_t *out_rec_open, int64_t *out_open, ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The same audit on the samples of the ideal rollout, which are never materialised: the
+ * shrinking-horizon frames (T < ph) build their constraints from ccmpc_ideal_minkowski_cycle's
+ * rollout, which exists only in registers, so there is no store for ccmpc_risk_audit to read.
+ *
+ * The contract: the outputs equal those of ccmpc_ideal_rollout (Z = NULL, the same prev_mean,
+ * prev_cov, T_src, src_cell, T, n_samples, x0, seed and rng_cell) followed by ccmpc_risk_audit
+ * on that store with cell_cnt[c] = n_samples for every cell and the same plan, cell_plan, rec,
+ * rec_kind and R.  Consequences:
+ *  - every count is equal count for count and out_min_d2 is equal bit for bit: the samples are
+ *    regenerated in registers by the rollout's own arithmetic (a sample is a pure function of
+ *    (seed, rng_cell[c], i, t) and the source moments) and tested by the audit's own;
+ *  - out_status[c] (nullable) is the rollout's status, and a failed cell obeys the same
+ *    sentence: its slots are NaN from the first failed step on, and a NaN position is hit by
+ *    nothing (it does not enter out_min_d2 either) and protected by nothing (it is open for
+ *    every record of that step);
+ *  - sharding invariance: the cells of one call give the same outputs as the same cells in
+ *    several calls with the matching rng_cell (and src_cell, x0, cell_plan, rec) slices.
+ * Rollout arguments as ccmpc_ideal_minkowski_cycle_ex: noise from Philox only, x0 and seed_dev
+ * nullable (seed_dev, device memory, overrides seed, so a captured graph audits a fresh seed
+ * per replay), rng_cell NULL = stream c.  Audit arguments and outputs as ccmpc_risk_audit with
+ * N = n_samples for every cell.
+ *
+ * CCMPC_ERR_ARG, all checked before any device call: T_src outside [2, 40], T outside
+ * [1, T_src - 1], n_cells outside [0, 65536), n_samples outside [1, 2^32), R not finite or
+ * <= 0, an unknown rec_kind when rec != NULL, plan and rec both NULL, a missing output of an
+ * enabled half.  n_cells == 0 returns CCMPC_OK.  The call is two launches (initial values,
+ * then the pass) with no workspace; it never synchronises and never reads device memory on
+ * the host, so it can be captured, and outputs need no initialisation.  Counts are integer
+ * atomics and out_min_d2 an unsigned integer minimum on the bit pattern of the non-negative
+ * double: no output bit depends on execution order.
+ * ------------------------------------------------------------------------------------- */
+int ccmpc_ideal_risk_audit(const double *prev_mean, const double *prev_cov, int64_t T_src,
+                           const int32_t *src_cell, int64_t n_cells, int64_t T,
+                           int64_t n_samples, const double *x0, uint64_t seed,
+                           const uint64_t *seed_dev, const int32_t *rng_cell,
+                           const double *plan, const int32_t *cell_plan, const void *rec,
+                           int rec_kind, double R, int64_t *out_hit, int64_t *out_hit_any,
+                           double *out_min_d2, int64_t *out_rec_open, int64_t *out_open,
+                           int32_t *out_status, ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Monte-Carlo calibration of half-space offsets to a risk budget: which offset would leave at
  * most cell_allow[c] particles of the cell open?  The companion of ccmpc_risk_audit (no
  * reference counterpart): an exact batched selection, one order statistic per record, on the
