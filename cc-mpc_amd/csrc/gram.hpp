@@ -180,6 +180,41 @@ __device__ __forceinline__ bool locate_item(int32_t item, const int64_t *__restr
   return false;
 }
 
+// locate_item for 1 <= n_cells <= 64, the one trip of the scan written out straight
+// (CCMPC_LOCATE_STRAIGHT, moments.hip's non-balanced RB = 1 kernels; the caller tests n_cells,
+// a uniform compare of a preloaded SGPR).  The three table loads are branch-free, as the
+// particle loads are: lanes past the last cell re-read cell n_cells - 1 and count zero items, and
+// without a reference table the third load re-reads the count's low word and is dropped.  In
+// the loop each load sat behind its own exec branch, the scan behind a wait inside the loop and
+// the read-outs behind a second one, and -- the loop having a back edge -- the wait counter's
+// bookkeeping kept a vmcnt(0) in front of the first later write to one of the tables' registers.
+// The same values in the same 32-bit arithmetic: the same item.
+__device__ __forceinline__ bool locate_item_straight(int32_t item, const int64_t *__restrict__ cnt,
+                                                     const int64_t *__restrict__ off, int n_cells,
+                                                     int lg_chunk, ItemLoc &loc,
+                                                     const int32_t *__restrict__ cell_ref,
+                                                     int64_t whole) {
+  const int lane = threadIdx.x & 63;
+  const int c = min(lane, n_cells - 1);
+  const int32_t *rp = cell_ref ? cell_ref + c : reinterpret_cast<const int32_t *>(cnt + c);
+  const int64_t n = cnt[c];
+  const int64_t o = off[c];
+  const int32_t rs_ld = *rp;
+  const int32_t rs = cell_ref ? rs_ld : 0;
+  const int32_t mine = lane < n_cells ? items_of(n, lg_chunk, whole) : 0;
+  const int32_t incl = wave_incl_scan_i32(mine);
+  if (item >= lane_i32(incl, 63)) return false;
+  const unsigned long long m = __ballot(incl > item);
+  const int l = __ffsll(static_cast<long long>(m)) - 1;
+  loc.cell = l;
+  loc.first = lane_i32(incl - mine, l);
+  loc.chunk_idx = item - loc.first;
+  loc.cnt = lane_i64(n, l);
+  loc.off = lane_i64(o, l);
+  loc.ref_sel = lane_i32(rs, l);
+  return true;
+}
+
 // ---- balanced mode (bandwidth-bound inputs) -------------------------------------------------
 // Power-of-two items leave the chip unevenly loaded once the input is large: C4 (640k
 // particles in 67 cells) made 693 items of 1024 particles for 768 resident slots, so 181 CUs

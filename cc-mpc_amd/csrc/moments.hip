@@ -446,6 +446,24 @@ __device__ __forceinline__ double prefetch_tail_landed(const MinkParams &mp, con
 #ifndef CCMPC_T_CONST
 #define CCMPC_T_CONST 1
 #endif
+// The front of the non-balanced RB = 1 kernels, written for the order of issue: what a wave
+// executes before it REQUESTS its first particle byte is serial time of the launch (nothing is in
+// flight yet that the instructions could hide behind).  CCMPC_LOCATE_STRAIGHT: n_cells <= 64
+// takes locate_item_straight (gram.hpp).  CCMPC_LOADS_FIRST: the shift's load and the first load
+// group go out as soon as their addresses exist; the rest of wave_range, the mask of dead rows and
+// the zeroing of the accumulators follow them (see `FRONT` in the item).  The shift's load stays
+// AHEAD of the group: vector loads return in order and the first MFMA needs the shift, so behind
+// the group it made the first sub-step wait for the whole group, which undid CCMPC_SUBSTEP_FENCE
+// (bench step +0.12 us against the parent, profiles/r24).  Neither knob gains alone beyond the
+// run-to-run spread; together 0.17 us on the bench step and 0.13 under the live timer -- while the
+// phase stamps show no gain in front of the publish and the kernel trace's average none: see
+// profiles/r24/README.md before building on this.
+#ifndef CCMPC_LOCATE_STRAIGHT
+#define CCMPC_LOCATE_STRAIGHT 1
+#endif
+#ifndef CCMPC_LOADS_FIRST
+#define CCMPC_LOADS_FIRST 1
+#endif
 //
 // Argument order: the first 14 dwords (56 bytes) are everything locate and the particle addresses
 // need -- the three tables, pos, ld, n_cells, lg_wq, whole, T -- because the build asks for them to
@@ -499,6 +517,105 @@ void moments_kernel(
     const int g = lane >> 4;
     const int64_t cnt = loc.cnt;
     double pre = (MINK && !CCMPC_TAIL_LATE) ? prefetch_tail(mp, loc, rows) : 0.0;
+    constexpr int DP = RB >= 3 ? CCMPC_DEPTH_BIG : kDepth;
+    constexpr bool FRONT = CCMPC_LOADS_FIRST != 0 && RB == 1 && !BAL;
+    double sh[RB];
+    d4 acc[NACC][NT];
+    double s1[RB];
+    if constexpr (FRONT) {
+      // Written for issue order (CCMPC_LOADS_FIRST): in front of the first group's loads nothing
+      // is in flight that an instruction could hide behind, so only what the nine addresses need
+      // is computed there, and everything else a wave sets up follows the request.  The values
+      // are wave_range's and load_group's: the same addresses, the same bits.
+      constexpr int GS = 4 * W * S;  // 64 particles: a load group
+      static_assert(RB == 1 && GS == 64, "the front is written for RB = 1");
+      // a whole-cell item longer than a chunk deals its load groups round-robin (below)
+      const bool rr = b - a > (int64_t(1) << lg_chunk);
+      const int64_t p0 = a + (rr ? int64_t(w) * GS : int64_t(w) << lg_wq);  // uniform, scalar
+      const bool live0 = r < rows;
+      int64_t row_at = static_cast<int64_t>(live0 ? r : 0) * ld + loc.off;
+      const P *rowp[RB];
+      bool live[RB] = {live0};
+      typename LaneVec<P, W>::type buf[DP][S][RB];
+      int64_t p1, ngroups, st;
+      // everything else, behind the request (and, a wave without particles, in its place)
+      auto behind = [&](bool particles, double x0) {
+        // the row's offset and the zero are named behind the fence, so that neither the ring's
+        // row pointer nor the accumulators' moves can be scheduled ahead of it
+        double zero = 0.0;
+        asm volatile("" : "+v"(row_at), "+v"(zero));
+        rowp[0] = pos + row_at;
+        // the shift: x0, loaded ahead of the group where the wave has particles (cnt > 0 then)
+        if (particles)
+          sh[0] = live0 ? x0 : 0.0;
+        else
+          sh[0] = (live0 && cnt > 0) ? static_cast<double>(rowp[0][0]) : 0.0;
+        // what is left of wave_range
+        st = rr ? G::NW * GS : GS;
+        p1 = (rr || p0 + (int64_t(1) << lg_wq) >= b) ? b : p0 + (int64_t(1) << lg_wq);
+        const uint64_t len = static_cast<uint64_t>(p1 - p0);
+        ngroups = !particles ? 0
+                  : static_cast<int64_t>(rr ? (len + (G::NW * GS - 1)) / (G::NW * GS)
+                                            : (len + (GS - 1)) / GS);
+#pragma unroll
+        for (int x = 0; x < NACC; ++x)
+#pragma unroll
+          for (int t = 0; t < NT; ++t) acc[x][t] = d4{zero, zero, zero, zero};
+        s1[0] = zero;
+      };
+      if (p0 < b) {  // uniform: the wave has particles (wave_range's ngroups > 0)
+        // The group's addresses: row and item base in 64 bits once, the lane's part and the
+        // clamp to the wave's last aligned run as 32-bit indices within the group.  p0 is a
+        // multiple of 4, so ((p1 - 1) & ~3) - p0 = ((p1 - p0) - 1) & ~3, and p1 - p0 is
+        // min(b - p0, wq) (round-robin: b - p0); a group's last run starts at GS - 4.
+        const P *gb = pos + (row_at + p0);
+        const uint32_t cap = rr ? uint32_t(GS) : min(uint32_t(GS), uint32_t(1) << lg_wq);
+        const uint64_t rem = static_cast<uint64_t>(b - p0);
+        const uint32_t len32 = rem < uint64_t(cap) ? static_cast<uint32_t>(rem) : cap;
+        const uint32_t qlast = (len32 - 1u) & ~uint32_t(W - 1);
+        // the shift first: branch-free (the row pointer of a dead row is row 0's), first used
+        // at the first MFMA, and the loads return in this order
+        const double x0 = static_cast<double>(pos[row_at]);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          const uint32_t q = min(static_cast<uint32_t>(4 * W * s + W * g), qlast);
+#if CCMPC_PROBE & 2  // diagnostic build only: every lane re-reads one cached run
+          LaneVec<P, W>::load(pos + row_at + (q & (W - 1)), buf[0][s][0]);
+#else
+          LaneVec<P, W>::load(gb + q, buf[0][s][0]);
+#endif
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        behind(true, x0);
+#pragma unroll
+        for (int d = 1; d < DP - 1; ++d) load_group<P, RB, S, W>(buf[d], rowp, p0 + d * st, p1, g);
+        if (MINK && CCMPC_TAIL_LATE) {  // the fence keeps its address and its scalar wait down here
+          __builtin_amdgcn_sched_barrier(0);
+          pre = prefetch_tail(mp, loc, rows);
+        }
+        // the ring of DP load groups, as below
+        int64_t gi = 0;
+        for (; gi + DP <= ngroups; gi += DP) {
+#pragma unroll
+          for (int d = 0; d < DP; ++d) {
+            load_group<P, RB, S, W>(buf[(d + DP - 1) % DP], rowp, p0 + (gi + d + DP - 1) * st, p1,
+                                    g);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_group<P, RB, S, NACC, W>(buf[d], sh, live, p0 + (gi + d) * st, p1, g, acc, s1);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+#pragma unroll
+        for (int d = 0; d < DP - 1; ++d)  // the < DP groups left were loaded ahead
+          if (gi + d < ngroups)
+            mfma_group<P, RB, S, NACC, W>(buf[d], sh, live, p0 + (gi + d) * st, p1, g, acc, s1);
+      } else {
+        behind(false, 0.0);
+        if (MINK && CCMPC_TAIL_LATE) pre = prefetch_tail_landed(mp, loc, rows);
+      }
+    } else {
+    // every other instance, in the order it had (the text is left where it stood, so that a
+    // change to the front above cannot change these kernels' code)
     // a whole-cell item longer than a chunk deals its load groups round-robin, as balanced
     // items do, so every wave streams ~1/NW of the cell
     const bool rr = BAL || (b - a > (int64_t(1) << lg_chunk));
@@ -506,7 +623,6 @@ void moments_kernel(
                             : wave_range<false>(a, b, w, G::NW, int64_t(1) << lg_wq, 4 * W * S);
     const int64_t p1 = wr.p1;
 
-    double sh[RB];
     const P *rowp[RB];
     bool live[RB];
 #pragma unroll
@@ -517,12 +633,10 @@ void moments_kernel(
       sh[bb] = (live[bb] && cnt > 0) ? static_cast<double>(rowp[bb][0]) : 0.0;
     }
 
-    d4 acc[NACC][NT];
 #pragma unroll
     for (int x = 0; x < NACC; ++x)
 #pragma unroll
       for (int t = 0; t < NT; ++t) acc[x][t] = d4{0.0, 0.0, 0.0, 0.0};
-    double s1[RB];
 #pragma unroll
     for (int bb = 0; bb < RB; ++bb) s1[bb] = 0.0;
 
@@ -535,7 +649,6 @@ void moments_kernel(
 #if CCMPC_PRIO  // experiment: static priority for the second-dispatched half (MI355X_MICROARCH.md)
     if (G::NW == 8 && w >= 4) __builtin_amdgcn_s_setprio(CCMPC_PRIO);
 #endif
-    constexpr int DP = RB >= 3 ? CCMPC_DEPTH_BIG : kDepth;
     typename LaneVec<P, W>::type buf[DP][S][RB];
     if (ngroups > 0) {
       // ring of DP load groups: group g lives in buf[g % DP]; DP - 1 groups are in flight
@@ -564,6 +677,7 @@ void moments_kernel(
           mfma_group<P, RB, S, NACC, W>(buf[d], sh, live, wr.p0 + (gi + d) * st, p1, g, acc, s1);
     } else if (MINK && CCMPC_TAIL_LATE) {
       pre = prefetch_tail_landed(mp, loc, rows);  // a wave with no particles
+    }
     }
     PROBE_TS(2);
     PROBE_STREAM_END();
@@ -598,9 +712,19 @@ void moments_kernel(
     return;
   }
   ItemLoc loc;
-  if (!locate_item(blockIdx.x, cell_cnt, cell_off, n_cells, lg_chunk, loc,
-                   cell_ref, whole))
-    return;  // uniform
+  if (CCMPC_LOCATE_STRAIGHT != 0 && RB == 1 &&
+      __builtin_expect(static_cast<unsigned>(n_cells - 1) < 64u, 1)) {
+    if (!locate_item_straight(blockIdx.x, cell_cnt, cell_off, n_cells, lg_chunk, loc, cell_ref,
+                              whole))
+      return;  // uniform
+  } else {
+    if (!locate_item(blockIdx.x, cell_cnt, cell_off, n_cells, lg_chunk, loc,
+                     cell_ref, whole))
+      return;  // uniform
+    // nothing is in flight here, and saying so keeps the loop's pessimistic wait (a back edge:
+    // the counter's bookkeeping cannot tell) out of the path the two locates share from here on
+    if (CCMPC_LOCATE_STRAIGHT != 0 && RB == 1) __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+  }
   PROBE_TS(1);
   const int32_t nit = items_of(loc.cnt, lg_chunk, whole);
   const int64_t i0 = static_cast<int64_t>(loc.chunk_idx) << lg_chunk;
