@@ -228,6 +228,46 @@ __device__ __forceinline__ void pair_of(int p, int &t, int &tau) {
   tau = p - tt * (tt - 1) / 2;
 }
 
+// The same map as a table where the horizon is a compile-time constant with at most 32 pairs
+// (TC <= 8): t in 4-bit fields of two 64-bit constants (pairs 0 .. 15 and 16 .. 31), the row's
+// start t (t - 1) / 2 in 8-bit fields of a third, indexed by t.  Two selects, two 64-bit shifts and
+// two masks in place of the closed form's float square root with its fix-up and two integer
+// multiplies, which stood at the head of every record's chain.  p must be below TC (TC - 1) / 2.
+// Build knob (0: the closed form everywhere).
+#ifndef CCMPC_PAIR_TABLE
+#define CCMPC_PAIR_TABLE 1
+#endif
+template <int TC>
+struct PairTable {
+  static constexpr int P = TC * (TC - 1) / 2;
+  static constexpr bool kFits = CCMPC_PAIR_TABLE != 0 && TC >= 2 && P <= 32;
+  static constexpr uint64_t t_word(int w) {
+    uint64_t x = 0;
+    for (int t = 1; t < TC; ++t)
+      for (int tau = 0; tau < t; ++tau) {
+        const int p = t * (t - 1) / 2 + tau;
+        if ((p >> 4) == w) x |= static_cast<uint64_t>(t) << (4 * (p & 15));
+      }
+    return x;
+  }
+  static constexpr uint64_t start_word() {
+    uint64_t x = 0;
+    for (int t = 1; t < TC && t < 8; ++t) x |= static_cast<uint64_t>(t * (t - 1) / 2) << (8 * t);
+    return x;
+  }
+};
+template <int TC>
+__device__ __forceinline__ void pair_of_tc(int p, int &t, int &tau) {
+  if constexpr (PairTable<TC>::kFits) {
+    constexpr uint64_t lo = PairTable<TC>::t_word(0), hi = PairTable<TC>::t_word(1);
+    constexpr uint64_t start = PairTable<TC>::start_word();
+    t = static_cast<int>(((p < 16 ? lo : hi) >> (4 * (p & 15))) & 15);
+    tau = p - static_cast<int>((start >> (8 * t)) & 255);
+  } else {
+    pair_of(p, t, tau);
+  }
+}
+
 
 // 16-byte store of two adjacent record fields (records are 128-byte aligned).
 static_assert(sizeof(ccmpc_halfspace) == 128, "record size");
@@ -353,7 +393,9 @@ __device__ void minkowski_pair(const double *C, const double *mu, const double *
   const int rows = TC ? 2 * TC : rows_arg;
   // the tangent frame: computed ahead of the MVOE fixed points (straight-line code the
   // scheduler overlaps with the pair-moment chain; after the data-dependent loops it would be
-  // pure latency)
+  // pure latency).  The compiler still sinks |n|'s square root behind the second loop and each
+  // `ok` flag's chain behind its loop; holding them in front with an empty asm was built and
+  // measured 0.02-0.04 us on the bench step, inside the spread (profiles/r25), and is not kept.
   const double m0 = mu[2 * t], m1 = mu[2 * t + 1];
   const TangentFrame f = tangent_frame(m0, m1, ref[2 * t], ref[2 * t + 1]);
   const double m = f.m, n0 = f.n0, n1 = 1.0, proj = f.proj, nrm = f.nrm, na = f.na;
@@ -429,7 +471,7 @@ __device__ void minkowski_cell(const double *C, const double *mu, int T_arg, int
     if (tid < half) {
       if (tid < P) {
         int t, tau;
-        pair_of(tid, t, tau);
+        pair_of_tc<TC>(tid, t, tau);
         minkowski_pair<TC>(C, mu, ref, rows, t, tau, chi_r, chi_p, mp.R, mp.tol, mp.maxiter,
                            rec + tid);
       }
@@ -439,7 +481,7 @@ __device__ void minkowski_cell(const double *C, const double *mu, int T_arg, int
     if (lane >= 64) return;
     for (int p = lane; p < P; p += 64) {
       int t, tau;
-      pair_of(p, t, tau);
+      pair_of_tc<TC>(p, t, tau);
       const double lb = pair_lower_bound(pair_moments(C, rows, t, tau), gamma);
       lb_s[p] = lb;
       rec[p].lower_bound = lb;
@@ -456,7 +498,7 @@ __device__ void minkowski_cell(const double *C, const double *mu, int T_arg, int
   const int base = lb_side ? tid - half : tid, stride = half ? half : nthreads;
   for (int p = base; p < P; p += stride) {
     int t, tau;
-    pair_of(p, t, tau);
+    pair_of_tc<TC>(p, t, tau);
     if (lb_side || !half) {
       const double lb = pair_lower_bound(pair_moments(C, rows, t, tau), gamma);
       lb_s[p] = lb;

@@ -773,6 +773,31 @@ inline bool tree_layout(void *ws, size_t ws_bytes, int64_t max_items, int64_t n_
 // profiles/r08): clamping the index of the loads past slab n - 1 re-read that slab up to 15
 // times, and a 7-slab root took as long as a 16-slab one.  They are now cut off by the buffer
 // descriptor's size instead: C2 cycle 10.26 -> 10.03 us (profiles/r08/ab/variants_headline.log).
+// CCMPC_GATHER_ORDERED (the gathers that pass ORD: the root gather of moments_kernel's RB = 1
+// instances): the kFanIn loads go out in SUMMING order.  Left to the scheduler they go out in the
+// order their address registers came to be -- slab 0's load 12th of 16 at the headline instance --
+// and the fixed-order sum ((v0 + v1) + v2) + ... cannot start before slab 0 is there: most of its
+// chained adds ran behind the last load instead of under the loads still in flight.  Held as r22
+// holds its sub-steps: a scheduling fence behind each load and an empty asm on the offset the next
+// load is formed from (a fence alone does not keep an address computation, and the load behind
+// it, from being formed early).  Same loads, same sum.
+#ifndef CCMPC_GATHER_ORDERED
+#define CCMPC_GATHER_ORDERED 1
+#endif
+template <bool ORD>
+__device__ __forceinline__ void load_slabs(__amdgpu_buffer_rsrc_t rs, int at, int E,
+                                           double2 (&v)[kFanIn]) {
+#pragma unroll
+  for (int i = 0; i < kFanIn; ++i) {
+    v[i] = ld2_sc1(rs, at + 8 * (i * E));
+    if (ORD) {
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(at));
+    }
+  }
+}
+
+template <bool ORD = false>
 __device__ __forceinline__ double2 sum_group2(const double *__restrict__ slab0, int64_t n, int E,
                                               int e) {
   double2 v[kFanIn];
@@ -780,8 +805,7 @@ __device__ __forceinline__ double2 sum_group2(const double *__restrict__ slab0, 
   // buffer unit answers them with zeros and sends nothing to memory
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<double *>(slab0), 0, static_cast<int>(n) * E * 8, 0x00020000);
-#pragma unroll
-  for (int i = 0; i < kFanIn; ++i) v[i] = ld2_sc1(rs, 8 * (i * E + e));
+  load_slabs<ORD>(rs, 8 * e, E, v);
   double2 s = v[0];
 #pragma unroll
   for (int i = 1; i < kFanIn; ++i) {
@@ -1041,7 +1065,8 @@ __host__ __device__ constexpr int gather_part_doubles(int E) {
 //    lanes l and l + 32 of one wave and meet by a cross-lane move, G0 + G1 in the lower lane:
 //    no LDS meeting point, one barrier less, the same bits.
 // The branch on root_n is workgroup-uniform.  Ends with a barrier.
-template <typename Sch, int NTH, int TC = 0>
+// ORD: the loads of a group in summing order (CCMPC_GATHER_ORDERED, above).
+template <typename Sch, int NTH, int TC = 0, bool ORD = false>
 __device__ __forceinline__ void gather_root(const double *__restrict__ root, int32_t root_n,
                                             int rows_arg, double *dst_lds, double *part_lds) {
   constexpr int E = Sch::E, GRAM = Sch::GRAM, H = Sch::GRAM / 2;
@@ -1054,10 +1079,10 @@ __device__ __forceinline__ void gather_root(const double *__restrict__ root, int
     // (a root wider than kRootFanIn exists only at the tree's depth bound; it, and a caller
     // with no LDS for the groups, passing part_lds = nullptr, go group by group in each thread)
     for (int e = 2 * tid; e < E; e += 2 * nth) {
-      double2 s = sum_group2(root, min(root_n, kFanIn), E, e);
+      double2 s = sum_group2<ORD>(root, min(root_n, kFanIn), E, e);
       for (int k = kFanIn; k < root_n; k += kFanIn) {  // fixed order: deterministic
-        const double2 t = sum_group2(root + static_cast<int64_t>(k) * E, min(root_n - k, kFanIn),
-                                     E, e);
+        const double2 t = sum_group2<ORD>(root + static_cast<int64_t>(k) * E,
+                                          min(root_n - k, kFanIn), E, e);
         s.x += t.x;
         s.y += t.y;
       }
@@ -1081,8 +1106,7 @@ __device__ __forceinline__ void gather_root(const double *__restrict__ root, int
       const int n_q = q ? root_n - kFanIn : kFanIn;
       const int at = 8 * (q * kFanIn * E + (e < 0 ? 0 : e));
       double2 v[kFanIn];
-#pragma unroll
-      for (int i = 0; i < kFanIn; ++i) v[i] = ld2_sc1(rs, at + 8 * (i * E));
+      load_slabs<ORD>(rs, at, E, v);
       double2 g = v[0];
 #pragma unroll
       for (int i = 1; i < kFanIn; ++i) {

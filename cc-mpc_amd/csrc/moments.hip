@@ -328,6 +328,9 @@ struct EpilogueLds {
 
 // TC: the compile-time horizon (0 = the run-time T), handed on to every helper that takes T or
 // the row count.
+#ifndef CCMPC_TAIL_LANDED
+#define CCMPC_TAIL_LANDED 1
+#endif
 template <typename Sch, int NTH, bool MINK, bool COV_IN_LDS, bool DEFER, int TC = 0,
           typename Publish>
 __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &loc, int32_t nit,
@@ -337,6 +340,8 @@ __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &lo
                                               double *__restrict__ out_cov, const MinkParams &mp,
                                               const EpilogueLds &L) {
   constexpr int E = Sch::E;
+  // the last arriver's path in issue order (profiles/r25): the RB = 1 instances of moments_kernel
+  constexpr bool kLastOrder = std::is_same<Sch, Scheme16<1>>::value;
   const int T = TC ? TC : T_arg;
   const int cell = loc.cell, rows = 2 * T;
   const double o0 = origin ? origin[2 * cell] : 0.0, o1 = origin ? origin[2 * cell + 1] : 0.0;
@@ -358,9 +363,20 @@ __device__ __forceinline__ void cell_epilogue(Publish publish, const ItemLoc &lo
                                          &root, &root_n);
     PROBE_TS(4);
     if (!last) return;
-    gather_root<Sch, NTH, TC>(root, root_n, rows, L.slab, L.cov);  // the exchange buffer is free
+    gather_root<Sch, NTH, TC, kLastOrder && CCMPC_GATHER_ORDERED != 0>(
+        root, root_n, rows, L.slab, L.cov);  // the exchange buffer is free
     PROBE_GATHERED();
   }
+  // CCMPC_TAIL_LANDED: tell the wait-count pass that nothing is in flight here.  Nothing is: the
+  // last arriver drained in arrive_last and has used every gathered value, the whole-cell path has
+  // used every particle, and prefetch_tail's load returned ahead of them.  But the pass cannot see
+  // arrive_last's inline-asm drain, and a load whose value some threads never use (prefetch_tail's
+  // in threads past 2T + 2) stays pending in its books; when the half-space tail reuses that
+  // register it put a full vmcnt(0) at the head of every record's chain -- behind the finaliser's
+  // global stores of mean and cov, which count in vmcnt, so the chain began with their
+  // acknowledgement.  The wait here finds nothing and the one in the tail goes.
+  if (kLastOrder && CCMPC_TAIL_LANDED != 0 && MINK)
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
   finalize_cell<Sch, NTH, TC>([&](int e) { return double2{L.slab[e], L.slab[e + 1]}; }, loc.cnt,
                               T, L.shift, L.S, o0, o1, mean, cov, L.mean,
                               COV_IN_LDS ? L.cov : nullptr, L.slab + Sch::GRAM);
