@@ -189,7 +189,7 @@ class CycleArgs(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_size_t), ("ref_traj", _P), ("cell_ref", _P),
                 ("cell_risk", _P), ("R", ctypes.c_double), ("tol", ctypes.c_double),
                 ("out_mean", _P), ("out_cov", _P), ("out_rec", _P), ("out_prob_lower", _P),
-                ("stream", _P)]
+                ("stream", _P), ("slot_cap", ctypes.c_int64)]
 
 
 class CcmpcError(RuntimeError):

@@ -76,11 +76,16 @@ class MinkowskiCycle:
         self.rec = torch.empty((C, P, 128), dtype=torch.uint8, device=self.device)
         self.prob_lower = torch.empty((C, T), dtype=torch.float64, device=self.device)
         self.ws = engine.Workspace(self.device)
-        self.ws.get(engine._lib.load().ccmpc_moments_workspace_bytes(T, C, store.n_bound))
+        self.ws.get(engine._lib.load().ccmpc_moments_workspace_bytes(T, C, store.ws_bound))
         self.graph = None
 
     def run(self):
-        """One launch: moments + every (cell, t, tau) half-space (ccmpc_minkowski_cycle)."""
+        """One launch: moments + every (cell, t, tau) half-space (ccmpc_minkowski_cycle).  On a
+        slotted store through the argument struct, which carries slot_cap (the positional entry
+        point keeps its signature and reads the cell tables)."""
+        if self.store.slot_cap:
+            self.bind().launch()
+            return
         engine.minkowski_cycle(self.store, self.ref, self.risk, cell_ref=self.cell_ref,
                                R=self.R, tol=self.tol,
                                maxiter=self.maxiter, workspace=self.ws, out_mean=self.mean,
@@ -95,7 +100,7 @@ class MinkowskiCycle:
         from . import _lib as L
         lib = engine._lib.load()
         st = self.store
-        ws = self.ws.get(lib.ccmpc_moments_workspace_bytes(self.T, st.n_cells, st.n_bound))
+        ws = self.ws.get(lib.ccmpc_moments_workspace_bytes(self.T, st.n_cells, st.ws_bound))
         p = engine._p
         self._fn = lib.ccmpc_minkowski_cycle_args
         self._argst = L.CycleArgs(
@@ -105,7 +110,7 @@ class MinkowskiCycle:
             workspace_bytes=ws.numel(), ref_traj=p(self.ref), cell_ref=p(self.cell_ref),
             cell_risk=p(self.risk), R=float(self.R), tol=float(self.tol), out_mean=p(self.mean),
             out_cov=p(self.cov), out_rec=p(self.rec), out_prob_lower=p(self.prob_lower),
-            stream=engine._stream())
+            stream=engine._stream(), slot_cap=int(getattr(st, "slot_cap", 0)))
         self._args = (ctypes.addressof(self._argst),)
         self._keep = ws
         return self

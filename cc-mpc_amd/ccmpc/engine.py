@@ -63,6 +63,92 @@ def _round_to(x, a):
     return (int(x) + a - 1) // a * a
 
 
+# The slotted layout (ParticleStore.slot_cap > 0): every cell owns slot_cap columns, so a cell's
+# start is c * slot_cap and the cycle kernel's short-horizon instances form their first particle
+# addresses from the workgroup index alone (moments.hip, SLOT).  SLOT_CHUNK is the largest item
+# the non-balanced RB = 1 path cuts (4 waves of 2^6 particles: CCMPC_LG_NW1 and the wave quota
+# below the balanced-mode bound); a slot is a whole number of them, and the library checks that
+# against the chunk it picks.  from_cells chooses the layout by itself only where the launch stays
+# small and the slots are not mostly air (slot_rule).
+SLOT_CHUNK = 256
+SLOT_MAX_CELLS = 64          # the straight locate's range: the launches the front was written for
+SLOT_MAX_ITEMS = 256         # at most one workgroup per CU, dead ones included
+SLOT_MAX_T = 8               # the RB = 1 path
+SLOT_MAX_BOUND = 1 << 18     # above it the launch is in balanced mode
+SLOT_MIN_FILL = 0.4          # total / (n_cells * slot_cap): see slot_rule
+
+
+def _lcm(a, b):
+    import math
+    return a * b // math.gcd(a, b)
+
+
+def slot_capacity(counts, align=None):
+    """The smallest slot that holds every cell: max(count) rounded up to the store alignment and
+    to SLOT_CHUNK, at least one chunk."""
+    al = STORE_ALIGN if align is None else int(align)
+    unit = _lcm(al, SLOT_CHUNK)
+    return max(_round_to(max([int(c) for c in counts] + [0]), unit), unit)
+
+
+def slot_rule(counts, T, n_bound, align=None):
+    """The slot capacity from_cells picks by itself, or 0 for the packed layout.  Slots where the
+    launch has at most SLOT_MAX_CELLS cells and SLOT_MAX_ITEMS workgroups (one per CU, so that
+    the workgroups without particles cost no second round), takes the RB = 1 path and is not in
+    balanced mode -- and where the cells fill at least SLOT_MIN_FILL of their slots: a slotted
+    store is n_cells * slot_cap wide whatever the cells hold, every copy of it and every row
+    stride grows with that, and every chunk of a slot past its cell's last is a workgroup
+    launched to exit.  C2, the sparsest store measured (nine cells of 600 .. 5000 in slots of
+    5120: 0.43), is inside; below that nothing was measured, so such stores stay packed."""
+    counts = [int(c) for c in counts]
+    if not counts or len(counts) > SLOT_MAX_CELLS or T > SLOT_MAX_T or n_bound > SLOT_MAX_BOUND:
+        return 0
+    cap = slot_capacity(counts, align)
+    if len(counts) * cap // SLOT_CHUNK > SLOT_MAX_ITEMS:
+        return 0
+    if sum(counts) < SLOT_MIN_FILL * len(counts) * cap:
+        return 0
+    return cap
+
+
+def store_layout(counts, capacity=None, align=None, slot_cap=0):
+    """(offsets, n_bound, ld) of a ParticleStore: host arithmetic only.  n_bound is the packed
+    walk's end (or the capacity) in either layout."""
+    counts = [int(c) for c in counts]
+    al = STORE_ALIGN if align is None else int(align)
+    if al < 4 or al % 4:
+        raise ValueError("store alignment must be a multiple of 4 particles")
+    offs, cur = [], 0
+    for c in counts:
+        offs.append(cur)
+        cur = _round_to(cur + max(c, 0), al)
+    n_bound = cur if capacity is None else max(cur, int(capacity))
+    ld = max(_round_to(n_bound, al), al)
+    slot_cap = int(slot_cap)
+    if slot_cap:
+        if slot_cap < 0 or slot_cap % al or slot_cap % SLOT_CHUNK:
+            raise ValueError(f"slot_cap must be a positive multiple of {al} and {SLOT_CHUNK}")
+        if counts and max(counts) > slot_cap:
+            raise ValueError(f"a cell of {max(counts)} particles in slots of {slot_cap}")
+        offs = [j * slot_cap for j in range(len(counts))]
+        ld = max(ld, len(counts) * slot_cap)
+    return offs, n_bound, ld
+
+
+def cells_image(cells, offsets, ld, dtype=torch.float64, origin=None):
+    """The host image [2T, ld] of a store holding `cells` at `offsets` (zero elsewhere)."""
+    T = cells[0].shape[1]
+    host = np.zeros((2 * T, ld), dtype=np.float64 if dtype == torch.float64 else np.float32)
+    for j, c in enumerate(cells):
+        c = np.asarray(c, dtype=np.float64)
+        if origin is not None:
+            c = c - np.asarray(origin, dtype=np.float64).reshape(-1, 2)[j]
+        n = c.shape[0]
+        o = offsets[j]
+        host[:, o:o + n] = c.transpose(1, 2, 0).reshape(2 * T, n)
+    return host
+
+
 class ParticleStore:
     """Plane-major SoA particle clouds of several cells (see include/ccmpc.h).
 
@@ -70,22 +156,20 @@ class ParticleStore:
     Cell offsets and ld are multiples of `align` particles (STORE_ALIGN = 32 by default; the
     kernels need a multiple of 4: 16-byte vector loads).
     F64 stores hold world coordinates; F32 stores hold coordinates relative to ``origin[j]``.
+
+    slot_cap = 0: cells packed one behind the other.  slot_cap > 0: the slotted layout, every
+    cell_off[j] == j * slot_cap, slot_cap a multiple of the alignment and of SLOT_CHUNK and at
+    least max(counts), ld >= n_cells * slot_cap.  n_bound is the same in both (the particle total
+    or capacity): it picks the kernels' item size, so both layouts cut the same items.
     """
 
     def __init__(self, T, counts, dtype=torch.float64, device="cuda", origin=None,
-                 capacity=None, align=None):
+                 capacity=None, align=None, slot_cap=0):
         self.device = require_device(device)
         self.T = int(T)
         counts = [int(c) for c in counts]
-        al = STORE_ALIGN if align is None else int(align)
-        if al < 4 or al % 4:
-            raise ValueError("store alignment must be a multiple of 4 particles")
-        offs, cur = [], 0
-        for c in counts:
-            offs.append(cur)
-            cur = _round_to(cur + max(c, 0), al)
-        self.n_bound = cur if capacity is None else max(cur, int(capacity))
-        self.ld = max(_round_to(self.n_bound, al), al)
+        offs, self.n_bound, self.ld = store_layout(counts, capacity, align, slot_cap)
+        self.slot_cap = int(slot_cap)
         self.dtype = dtype
         self.pos = torch.zeros((2 * self.T, self.ld), dtype=dtype, device=self.device)
         self.counts = counts
@@ -106,24 +190,30 @@ class ParticleStore:
     def ccmpc_dtype(self):
         return F64 if self.dtype == torch.float64 else F32
 
+    @property
+    def ws_bound(self):
+        """The particle bound to size a moments workspace with: a slotted launch keeps one slab
+        per chunk of every slot (ccmpc_cycle_args in include/ccmpc.h)."""
+        return max(self.n_bound, self.n_cells * self.slot_cap)
+
     @classmethod
-    def from_cells(cls, cells, device="cuda", dtype=torch.float64, origin=None, capacity=None):
+    def from_cells(cls, cells, device="cuda", dtype=torch.float64, origin=None, capacity=None,
+                   slots=None):
         """cells: list of (N_j, T, 2) arrays (the reference's pred_positions[k] layout).
         For a float32 store, ``origin`` (n_cells, 2) is subtracted in float64 before the cast.
-        ``capacity`` raises the particle bound the kernels are sized for (n_particles_bound)."""
+        ``capacity`` raises the particle bound the kernels are sized for (n_particles_bound).
+        ``slots``: None picks the layout by slot_rule, True forces the slotted layout (at
+        slot_capacity), False the packed one."""
         T = cells[0].shape[1]
-        store = cls(T, [c.shape[0] for c in cells], dtype=dtype, device=device, origin=origin,
-                    capacity=capacity)
-        host = np.zeros((2 * T, store.ld), dtype=np.float64 if dtype == torch.float64
-                        else np.float32)
-        for j, c in enumerate(cells):
-            c = np.asarray(c, dtype=np.float64)
-            if origin is not None:
-                c = c - np.asarray(origin, dtype=np.float64).reshape(-1, 2)[j]
-            n = c.shape[0]
-            o = store.offsets[j]
-            host[:, o:o + n] = c.transpose(1, 2, 0).reshape(2 * T, n)
-        store.pos.copy_(torch.from_numpy(host))
+        counts = [c.shape[0] for c in cells]
+        if slots is None:
+            cap = slot_rule(counts, T, store_layout(counts, capacity)[1])
+        else:
+            cap = slot_capacity(counts) if slots else 0
+        store = cls(T, counts, dtype=dtype, device=device, origin=origin, capacity=capacity,
+                    slot_cap=cap)
+        store.pos.copy_(torch.from_numpy(cells_image(cells, store.offsets, store.ld, dtype,
+                                                     origin)))
         return store
 
     def sync_counts(self):

@@ -477,6 +477,27 @@ __device__ __forceinline__ double prefetch_tail_landed(const MinkParams &mp, con
 #ifndef CCMPC_LOCATE_STRAIGHT
 #define CCMPC_LOCATE_STRAIGHT 1
 #endif
+// The slotted front (below; 0 = never picked: a slotted store then runs the packed path).
+#ifndef CCMPC_SLOT_FRONT
+#define CCMPC_SLOT_FRONT 1
+#endif
+// What a SLOT instance gets where the others get cell_off: the slot's capacity in particles and
+// the multiply-high constant of items_per_slot = slot_cap >> lg_chunk.  A constant and not a
+// shift: the capacity is max(cnt) rounded up to a chunk, and rounding the item count up to a
+// power of two as well would cost up to twice the workgroups and the store's width (C2: 20 items
+// per slot, 180 workgroups; 32 would be 288, past one per CU).  magic = floor(2^31 / ips) + 1
+// fits a dword for every ips >= 1, and mulhi(2 i, magic) = floor(i / ips) for every i < 2^31 /
+// ips: the error term 2 i (magic - 2^31 / ips) / 2^32 stays below 1 / ips.
+// The two travel as ONE 64-bit scalar (capacity low, constant high): a struct passed by value is
+// not preloaded, and nothing behind it either -- the front then began with a wait for an
+// argument load.
+using SlotArg = uint64_t;
+inline SlotArg slot_arg(int64_t slot_cap, int64_t ips) {
+  const uint64_t magic = (uint64_t(1) << 31) / static_cast<uint64_t>(ips) + 1u;
+  return static_cast<uint64_t>(static_cast<uint32_t>(slot_cap)) | (magic << 32);
+}
+template <bool SLOT>
+using OffArg = std::conditional_t<SLOT, SlotArg, const int64_t *__restrict__>;
 #ifndef CCMPC_LOADS_FIRST
 #define CCMPC_LOADS_FIRST 1
 #endif
@@ -487,12 +508,19 @@ __device__ __forceinline__ double prefetch_tail_landed(const MinkParams &mp, con
 // 16 user SGPRs less the two of the argument pointer).  An argument past byte 56 is a scalar
 // load, and a use of one ahead of locate puts a wait for a cold line in front of the table
 // loads: keep origin, tree, the outputs and mp behind the stream.
-template <typename P, int RB, bool MINK, bool BAL, int TC = 0>
+//
+// SLOT (CCMPC_SLOT_FRONT; the non-balanced RB = 1 instances on a slotted store, cell_off[c] =
+// c * slot_cap): the cell, the chunk and with them the shift's and the first group's addresses are
+// arithmetic on the workgroup index and two preloaded dwords, which take cell_off's place among
+// the fourteen (SlotArg).  The loads go out at wave start beside the one table load still needed,
+// cell_cnt[cell]; see `SLOT` in the item.  It follows TC so that the name's prefix stays what the
+// tools match.
+template <typename P, int RB, bool MINK, bool BAL, int TC = 0, bool SLOT = false>
 // The fused half-space tail needs a few more registers than the 128 of 4 waves/SIMD at RB = 1.
 __global__ __launch_bounds__(Geo<RB>::THREADS,
                              (MINK && RB == 1) ? 3 : Geo<RB>::MIN_WAVES_PER_SIMD)
 void moments_kernel(
-    const int64_t *__restrict__ cell_cnt, const int64_t *__restrict__ cell_off,
+    const int64_t *__restrict__ cell_cnt, OffArg<SLOT> cell_off,
     const int32_t *__restrict__ cell_ref, const P *__restrict__ pos, int64_t ld, int n_cells,
     int lg_wq, int32_t whole32, int T_arg, const double *__restrict__ origin, TreeLayout tree,
     double *__restrict__ out_mean, double *__restrict__ out_cov, MinkParams mp) {
@@ -528,10 +556,11 @@ void moments_kernel(
   const int lg_chunk = lg_wq + lg_waves_per_item(RB);
 
   // one work item: the cell's particles [a, b) -> partial Gram -> combine tree / finalise
-  auto item = [=](const ItemLoc &loc, int32_t nit, int64_t a, int64_t b) {
+  auto item = [=](const ItemLoc &loc_in, int32_t nit, int64_t a, int64_t b) {
     const int r = lane & 15;
     const int g = lane >> 4;
-    const int64_t cnt = loc.cnt;
+    ItemLoc loc = loc_in;  // SLOT: cnt, ref_sel, nit, a and b are known only behind the request
+    int64_t cnt = loc.cnt;
     double pre = (MINK && !CCMPC_TAIL_LATE) ? prefetch_tail(mp, loc, rows) : 0.0;
     constexpr int DP = RB >= 3 ? CCMPC_DEPTH_BIG : kDepth;
     constexpr bool FRONT = CCMPC_LOADS_FIRST != 0 && RB == 1 && !BAL;
@@ -546,14 +575,58 @@ void moments_kernel(
       constexpr int GS = 4 * W * S;  // 64 particles: a load group
       static_assert(RB == 1 && GS == 64, "the front is written for RB = 1");
       // a whole-cell item longer than a chunk deals its load groups round-robin (below)
-      const bool rr = b - a > (int64_t(1) << lg_chunk);
-      const int64_t p0 = a + (rr ? int64_t(w) * GS : int64_t(w) << lg_wq);  // uniform, scalar
+      bool rr = b - a > (int64_t(1) << lg_chunk);
+      int64_t p0 = a + (rr ? int64_t(w) * GS : int64_t(w) << lg_wq);  // uniform, scalar
       const bool live0 = r < rows;
       int64_t row_at = static_cast<int64_t>(live0 ? r : 0) * ld + loc.off;
       const P *rowp[RB];
       bool live[RB] = {live0};
       typename LaneVec<P, W>::type buf[DP][S][RB];
       int64_t p1, ngroups, st;
+      double x0s = 0.0;
+      if constexpr (SLOT) {
+        // The request, in issue order: the cell's count (and reference selector), the shift, the
+        // eight particle loads -- every address from preloaded arguments alone.  The wave's first
+        // group is columns (chunk << lg_chunk) + (w << lg_wq) + [0, GS) of the slot, in contiguous
+        // mode and (lg_wq = 6, the host's condition for this instance) in a whole cell's
+        // round-robin mode alike.  The loads are NOT clamped to the cell's last run: they stay
+        // inside the slot, which is allocated, and what is at or past p1 is masked in mfma_group
+        // as a clamped re-read is.  Nothing in front of the fence needs cnt.
+        const int64_t p0s =
+            (static_cast<int64_t>(loc.chunk_idx) << lg_chunk) + (int64_t(w) << lg_wq);
+        const int64_t n_ld = cell_cnt[loc.cell];
+        __builtin_amdgcn_sched_barrier(0);
+        x0s = static_cast<double>(pos[row_at]);
+        const P *gb = pos + (row_at + p0s);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+#if CCMPC_PROBE & 2  // diagnostic build only: every lane re-reads one cached run
+          LaneVec<P, W>::load(pos + row_at + ((W * g) & (W - 1)), buf[0][s][0]);
+#else
+          LaneVec<P, W>::load(gb + (4 * W * s + W * g), buf[0][s][0]);
+#endif
+        }
+        // the loads have no user on the paths that leave below: keep them from being sunk there
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        // the reference selector rides behind the request (the table may be absent: then the
+        // count's low word is re-read and dropped, as in locate_item_straight)
+        const int32_t *rp = cell_ref ? cell_ref + loc.cell
+                                     : reinterpret_cast<const int32_t *>(cell_cnt + loc.cell);
+        const int32_t rs_ld = *rp;
+        PROBE_TS(1);
+        cnt = n_ld;
+        loc.cnt = n_ld;
+        loc.ref_sel = cell_ref ? rs_ld : 0;
+        nit = items_of(cnt, lg_chunk, whole);
+        // no item: the chunk is past the cell's last, or past the first of a whole cell.  Uniform,
+        // and before this workgroup touches a counter, a slab or LDS; its loads are dropped.
+        if (loc.chunk_idx >= nit) return;
+        a = static_cast<int64_t>(loc.chunk_idx) << lg_chunk;
+        b = nit == 1 ? cnt : min(a + (int64_t(1) << lg_chunk), cnt);
+        rr = b - a > (int64_t(1) << lg_chunk);
+        p0 = p0s;
+      }
       // everything else, behind the request (and, a wave without particles, in its place)
       auto behind = [&](bool particles, double x0) {
         // the row's offset and the zero are named behind the fence, so that neither the ring's
@@ -562,7 +635,9 @@ void moments_kernel(
         asm volatile("" : "+v"(row_at), "+v"(zero));
         rowp[0] = pos + row_at;
         // the shift: x0, loaded ahead of the group where the wave has particles (cnt > 0 then)
-        if (particles)
+        if (SLOT)  // always loaded: column 0 of the slot, a particle where cnt > 0
+          sh[0] = (live0 && cnt > 0) ? x0 : 0.0;
+        else if (particles)
           sh[0] = live0 ? x0 : 0.0;
         else
           sh[0] = (live0 && cnt > 0) ? static_cast<double>(rowp[0][0]) : 0.0;
@@ -580,6 +655,9 @@ void moments_kernel(
         s1[0] = zero;
       };
       if (p0 < b) {  // uniform: the wave has particles (wave_range's ngroups > 0)
+        if constexpr (SLOT) {
+          behind(true, x0s);  // the request went out above
+        } else {
         // The group's addresses: row and item base in 64 bits once, the lane's part and the
         // clamp to the wave's last aligned run as 32-bit indices within the group.  p0 is a
         // multiple of 4, so ((p1 - 1) & ~3) - p0 = ((p1 - p0) - 1) & ~3, and p1 - p0 is
@@ -603,6 +681,7 @@ void moments_kernel(
         }
         __builtin_amdgcn_sched_barrier(0);
         behind(true, x0);
+        }
 #pragma unroll
         for (int d = 1; d < DP - 1; ++d) load_group<P, RB, S, W>(buf[d], rowp, p0 + d * st, p1, g);
         if (MINK && CCMPC_TAIL_LATE) {  // the fence keeps its address and its scalar wait down here
@@ -626,7 +705,7 @@ void moments_kernel(
           if (gi + d < ngroups)
             mfma_group<P, RB, S, NACC, W>(buf[d], sh, live, p0 + (gi + d) * st, p1, g, acc, s1);
       } else {
-        behind(false, 0.0);
+        behind(false, x0s);
         if (MINK && CCMPC_TAIL_LATE) pre = prefetch_tail_landed(mp, loc, rows);
       }
     } else {
@@ -715,6 +794,21 @@ void moments_kernel(
   };
 
   PROBE_TS(0);
+  if constexpr (SLOT) {
+    static_assert(RB == 1 && !BAL && CCMPC_LOADS_FIRST != 0, "the slotted front is RB = 1's");
+    // (cell, chunk) of this workgroup: a multiply-high, a multiply and a subtract of scalars
+    const uint32_t slot_cap = static_cast<uint32_t>(cell_off);
+    const uint32_t ips = slot_cap >> lg_chunk;
+    ItemLoc loc;
+    loc.cell = static_cast<int>(__umulhi(blockIdx.x << 1, static_cast<uint32_t>(cell_off >> 32)));
+    loc.first = static_cast<int32_t>(loc.cell * ips);
+    loc.chunk_idx = static_cast<int32_t>(blockIdx.x) - loc.first;
+    loc.off = static_cast<int64_t>(static_cast<uint32_t>(loc.cell) * slot_cap);  // < ld
+    loc.cnt = 0;
+    loc.ref_sel = 0;
+    (void)n_cells;
+    item(loc, 0, 0, 0);
+  } else {
   if (BAL) {
     ItemLoc loc;
     int64_t chunk;
@@ -746,6 +840,7 @@ void moments_kernel(
   const int64_t i0 = static_cast<int64_t>(loc.chunk_idx) << lg_chunk;
   const int64_t i1 = nit == 1 ? loc.cnt : min(i0 + (int64_t(1) << lg_chunk), loc.cnt);
   item(loc, nit, i0, i1);
+  }
 }
 
 // ---- Scheme4: f64 4x4x4_4b MFMA over 4-row blocks (T <= 12) -------------------------------
@@ -1199,6 +1294,43 @@ static int launch(const P *pos, int64_t ld, int T, const double *origin, const i
   return CCMPC_OK;
 }
 
+// The cycle on a slotted store (every cell_off[c] = c * slot_cap; SLOT in moments_kernel): one
+// workgroup per (cell, chunk of the slot), n_cells * slot_cap / chunk of them, and one slab per
+// such item (first = cell * items_per_slot), so the tree is laid out for that count and not for
+// max_items(n_cells, n_bound).  n_bound still picks lg_wq and the whole-cell cap, so the items
+// that do work are the packed launch's and hold the same particles in the same order.
+inline bool slot_front_takes(int64_t T, int64_t n_bound) {
+  // the non-balanced RB = 1 instances, at the wave quota where a whole cell's round-robin first
+  // group is the contiguous one (w * 64 = w << lg_wq)
+  return CCMPC_SLOT_FRONT != 0 && CCMPC_LOADS_FIRST != 0 && T <= 8 &&
+         !balanced_mode(n_bound) && store_lg_wave_quota(1, n_bound) == 6;
+}
+template <typename P>
+static int launch_slot(const P *pos, int64_t ld, int T, const double *origin, const int64_t *cnt,
+                       int n_cells, int64_t n_bound, int64_t slot_cap, void *ws, size_t ws_bytes,
+                       double *mean, double *cov, const MinkParams &mp, hipStream_t s) {
+  constexpr int threads = Geo<1>::THREADS;
+  const int lg_wq = store_lg_wave_quota(1, n_bound);
+  const int64_t chunk = int64_t(1) << store_lg_chunk(1, n_bound);
+  if (slot_cap <= 0 || slot_cap % chunk != 0 || slot_cap > INT32_MAX) return CCMPC_ERR_ARG;
+  const int64_t ips = slot_cap / chunk, items = n_cells * ips;
+  if (n_cells * slot_cap > ld || items >= (int64_t(1) << 30)) return CCMPC_ERR_ARG;
+  TreeLayout tree;
+  if (!tree_layout(ws, ws_bytes, items, n_cells, slab_doubles(1), tree)) return CCMPC_ERR_WORKSPACE;
+  const SlotArg slot = slot_arg(slot_cap, ips);
+  if (CCMPC_T_CONST != 0 && T == 8)
+    hipLaunchKernelGGL((moments_kernel<P, 1, true, false, 8, true>),
+                       dim3(static_cast<unsigned>(items)), dim3(threads), 0, s, cnt, slot,
+                       mp.cell_ref, pos, ld, n_cells, lg_wq, whole_cell_max(1, n_bound), T, origin,
+                       tree, mean, cov, mp);
+  else
+    hipLaunchKernelGGL((moments_kernel<P, 1, true, false, 0, true>),
+                       dim3(static_cast<unsigned>(items)), dim3(threads), 0, s, cnt, slot,
+                       mp.cell_ref, pos, ld, n_cells, lg_wq, whole_cell_max(1, n_bound), T, origin,
+                       tree, mean, cov, mp);
+  return CCMPC_OK;
+}
+
 template <typename P, int NB, bool MINK>
 static int launch4(const P *pos, int64_t ld, int T, const double *origin, const int64_t *off,
                    const int64_t *cnt, int n_cells, int64_t n_bound, void *ws, size_t ws_bytes,
@@ -1394,8 +1526,59 @@ extern "C" int ccmpc_minkowski_cycle(const void *positions, int dtype, int64_t l
                    "ccmpc_minkowski_cycle");
 }
 
+// slot_cap > 0: the store is slotted.  Where the slotted front takes the launch its conditions
+// are checked here, on the host, and a store that misses one is an error and launches nothing;
+// everywhere else (long horizons, balanced mode, CCMPC_SLOT_FRONT = 0) the packed path below runs,
+// which is right on a slotted store because its tables are honest.
 extern "C" int ccmpc_minkowski_cycle_args(const ccmpc_cycle_args *a) {
   CCMPC_REQUIRE(a, "null args");
+  CCMPC_REQUIRE(a->slot_cap >= 0, "bad slot_cap");
+  if (a->slot_cap > 0 && a->n_cells > 0 && a->T >= 1 &&
+      slot_front_takes(a->T, a->n_particles_bound)) {
+    // CHECK_STORE_ARGS' conditions, less the packed launch's workspace size (launch_slot lays
+    // out its own and says so), then the slot's
+    const int64_t T = a->T, n_cells = a->n_cells, n_particles_bound = a->n_particles_bound,
+                  ld = a->ld;
+    const int dtype = a->dtype;
+    const void *positions = a->positions;
+    void *workspace = a->workspace;
+    double *out_mean = a->out_mean, *out_cov = a->out_cov;
+    CCMPC_REQUIRE(n_cells < (1 << 30), "bad n_cells");
+    CCMPC_REQUIRE(positions && a->cell_off && a->cell_cnt && out_mean && out_cov, "null pointer");
+    CCMPC_REQUIRE(ld % 4 == 0 && ld > 0, "ld must be a positive multiple of 4");
+    CCMPC_REQUIRE(dtype == CCMPC_F64 || dtype == CCMPC_F32, "bad dtype");
+    CCMPC_REQUIRE(aligned(positions, 16), "positions must be 16-byte aligned");
+    CCMPC_REQUIRE(workspace && aligned(workspace, 16), "workspace must be 16-byte aligned");
+    CCMPC_REQUIRE(a->ref_traj && a->cell_risk && a->out_rec && a->out_prob_lower, "null pointer");
+    CCMPC_REQUIRE(a->maxiter >= 1, "maxiter must be >= 1");
+    const int64_t chunk = int64_t(1) << store_lg_chunk(1, n_particles_bound);
+    CCMPC_REQUIRE(a->slot_cap % chunk == 0, "slot_cap must be a multiple of the item chunk");
+    CCMPC_REQUIRE(a->slot_cap <= INT32_MAX && n_cells * a->slot_cap <= ld,
+                  "ld must hold n_cells slots");
+    const MinkParams mp{a->ref_traj, a->cell_ref, a->cell_risk, a->R, a->tol, a->maxiter,
+                        a->out_rec, a->out_prob_lower};
+    hipStream_t s = as_stream(a->stream);
+    const int rc =
+        dtype == CCMPC_F64
+            ? launch_slot(static_cast<const double *>(positions), ld, static_cast<int>(T),
+                          a->origin, a->cell_cnt, static_cast<int>(n_cells), n_particles_bound,
+                          a->slot_cap, workspace, a->workspace_bytes, out_mean, out_cov, mp, s)
+            : launch_slot(static_cast<const float *>(positions), ld, static_cast<int>(T),
+                          a->origin, a->cell_cnt, static_cast<int>(n_cells), n_particles_bound,
+                          a->slot_cap, workspace, a->workspace_bytes, out_mean, out_cov, mp, s);
+    if (rc != CCMPC_OK) {
+      set_error(std::string(__func__) + (rc == CCMPC_ERR_WORKSPACE
+                                             ? ": workspace too small for the slotted items"
+                                             : ": bad slotted store"));
+      return rc;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      set_error(std::string(__func__) + ": launch failed: " + hipGetErrorString(e));
+      return CCMPC_ERR_LAUNCH;
+    }
+    return CCMPC_OK;
+  }
   return ccmpc_minkowski_cycle(a->positions, a->dtype, a->ld, a->T, a->origin, a->cell_off,
                                a->cell_cnt, a->n_cells, a->n_particles_bound, a->workspace,
                                a->workspace_bytes, a->ref_traj, a->cell_ref, a->cell_risk, a->R,

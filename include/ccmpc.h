@@ -204,7 +204,16 @@ int ccmpc_minkowski_cycle(const void *positions, int dtype, int64_t ld, int64_t 
 /* The same call with its arguments in one struct, filled once by a caller that launches the
  * same cycle every step (the argument marshalling of a 22-argument foreign call is microseconds
  * of host time in front of every launch from an interpreter).  ccmpc_cycle_args_size() =
- * sizeof(ccmpc_cycle_args), for a binding to check its layout. */
+ * sizeof(ccmpc_cycle_args), for a binding to check its layout.
+ *
+ * slot_cap (the last field) is 0 for a packed store.  Above 0 the store is slotted: every
+ * cell_off[c] == c * slot_cap, slot_cap is a multiple of the launch's item chunk (256 particles at
+ * T <= 8) and at least every cell_cnt[c], and ld >= n_cells * slot_cap.  Short horizons (T <= 8)
+ * below the balanced-mode bound then run one workgroup per (cell, chunk of the slot) whose first
+ * particle loads do not wait for the cell tables.  The workspace holds one slab per such item:
+ * size it with ccmpc_moments_workspace_bytes(T, n_cells, max(n_particles_bound, n_cells *
+ * slot_cap)).  A slot_cap that is no multiple of the chunk or does not fit ld is CCMPC_ERR_ARG and
+ * launches nothing.  Every other launch ignores the field and reads the tables. */
 typedef struct ccmpc_cycle_args {
   const void *positions;
   int32_t dtype, maxiter;
@@ -222,6 +231,7 @@ typedef struct ccmpc_cycle_args {
   ccmpc_halfspace *out_rec;
   double *out_prob_lower;
   ccmpc_stream_t stream;
+  int64_t slot_cap;
 } ccmpc_cycle_args;
 int ccmpc_minkowski_cycle_args(const ccmpc_cycle_args *args);
 size_t ccmpc_cycle_args_size(void);

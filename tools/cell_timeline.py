@@ -39,6 +39,8 @@ def main():
     cyc = cycle.MinkowskiCycle(store, [len(o) for o in ovs], ref).bind()
     items = [1 if n <= WHOLE else -(-n // ITEM) for n in store.counts]
     first = np.concatenate(([0], np.cumsum(items)))
+    slot_items = getattr(store, "slot_cap", 0) // ITEM   # slotted: cell c's items start at c * this
+    n_wg = store.n_cells * slot_items if slot_items else first[-1]
     rows, enders, spans = [], [], []
     for _ in range(reps):
         for _ in range(3):
@@ -50,11 +52,12 @@ def main():
         torch.cuda.synchronize()
         buf = np.zeros(8192 * 8, np.uint64)
         assert lib.ccmpc_probe_timestamps(buf.ctypes.data_as(ctypes.c_void_p), 0) == 0
-        ts = buf.reshape(8192, 8).astype(np.int64)[:first[-1]]
+        ts = buf.reshape(8192, 8).astype(np.int64)[:n_wg]
         rel = (ts - ts[:, 0].min()) / 100.0
         row = []
         for c in range(store.n_cells):
-            r = rel[first[c]:first[c + 1]]
+            r = (rel[c * slot_items:c * slot_items + items[c]] if slot_items
+                 else rel[first[c]:first[c + 1]])
             last = int(np.argmax(r[:, 6]))           # the finaliser: the only one with a tail stamp
             row.append((r[:, 0].max(), r[:, 3].max(), r[last, 2], r[last, 4], r[last, 7],
                         r[last, 5], r[last, 6], r[last, 3]))

@@ -1,7 +1,9 @@
 """Per-workgroup phase timeline of one moments / cycle launch (needs the PROBE=4 build of
 libccmpc.so copied over the real one; see tools/probe_variants.sh).
 
-Slots (s_memrealtime, 100 MHz): 0 start, 1 located, 2 wave 0's stream loop done,
+Slots (s_memrealtime, 100 MHz): 0 start, 1 located (the slotted front: its first load group
+requested and the cell's count back -- the stamp's s_memrealtime returns behind the scalar loads),
+2 wave 0's stream loop done,
 3 combined + published, 4 tree climbed (or gave up), 5 finalised, 6 half-spaces done.
 A library that has ccmpc_probe_stream_end also gives the time the workgroup's LAST wave left its
 stream loop ("wg loop end / dur": what the combine's barrier waits for; slot 2 is wave 0's).
@@ -43,7 +45,12 @@ def one(name, what, dev, lib, back_to_back=1):
     torch.cuda.synchronize()
     assert lib.ccmpc_probe_timestamps(buf.ctypes.data_as(ctypes.c_void_p), 0) == 0
     ts = buf.reshape(MAXWG, SLOTS).astype(np.int64)
-    live = ts[:, 0] > 0
+    launched = ts[:, 0] > 0
+    # a slotted store launches a workgroup per chunk of every slot; those without an item leave
+    # behind slot 1 and publish nothing (slot 3 stays 0): they are counted, not timed
+    live = launched & (ts[:, 3] > 0)
+    if launched.sum() != live.sum():
+        print(f"   ({launched.sum() - live.sum()} of {launched.sum()} workgroups had no item)")
     wg = np.flatnonzero(live)
     ts = ts[live]
     wg_end = None
