@@ -160,6 +160,10 @@ SIGNATURES = {
     "ccmpc_risk_quantile_workspace_bytes": (_SZ, [_I64, ctypes.c_int, _I64]),
     "ccmpc_risk_quantile": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64, _I64,
                                            _P, ctypes.c_int, _D, _P, _P, _SZ, _P, _P, _P, _P]),
+    "ccmpc_ideal_risk_quantile_workspace_bytes": (_SZ, [_I64, ctypes.c_int, _I64]),
+    "ccmpc_ideal_risk_quantile": (ctypes.c_int, [_P, _P, _I64, _P, _I64, _I64, _I64, _P, _U64, _P,
+                                                 _P, _P, ctypes.c_int, _D, _P, _P, _SZ, _P, _P,
+                                                 _P, _P, _P]),
     "ccmpc_face_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "ccmpc_face_constraints": (ctypes.c_int, [_P, ctypes.c_int, _I64, _I64, _P, _P, _P, _I64,
                                               _I64, _P, _P, _P, _P, _P, ctypes.c_int, _D, _P,

@@ -1340,6 +1340,82 @@ def risk_quantile(store, rec, rec_kind, allow=None, R=risk.R_COLLISION, T=None, 
     return out
 
 
+def ideal_risk_quantile(prev_mean, prev_cov, src_cell, T, n_samples, rec, rec_kind, allow=None,
+                        R=risk.R_COLLISION, x0=None, seed=0, seed_dev=None, rng_cell=None,
+                        out=None):
+    """risk_quantile on the samples of the ideal rollout, which are never materialised
+    (ccmpc_ideal_risk_quantile): q, rhs and status equal, bit for bit, ideal_rollout(prev_mean,
+    prev_cov, src_cell, T, n_samples, x0=x0, seed=seed, rng_cell=rng_cell) followed by
+    risk_quantile on that store; every counting pass generates the samples again in registers.
+    Records of a failed cell from its first failed step on are SKIPPED.
+
+    Rollout arguments (src_cell, x0, seed, seed_dev, rng_cell) as ideal_risk_audit; rec /
+    rec_kind / allow / R as risk_quantile, with n_samples particles in every cell.
+    Returns (RiskQuantile, cell_status): cell_status [C] int32 is the rollout's.  out: a
+    previous call's (RiskQuantile, cell_status) pair, or a bare RiskQuantile (the status is then
+    not written and returned as None); nothing is allocated then, so the call can be captured.
+    Enqueues 17 launches on the current stream, never synchronises."""
+    lib = _lib.load()
+    dev = prev_mean.device
+    C = int(src_cell.shape[0])
+    T_src = int(prev_mean.shape[1])
+    T, n_samples = int(T), int(n_samples)
+    if not 1 <= T <= T_src - 1:
+        raise ValueError(f"T = {T} outside [1, {T_src - 1}] (the source horizon less one)")
+    if rec is None:
+        raise ValueError("ideal_risk_quantile needs records")
+    rec = _rec_bytes(rec, rec_kind, C)
+    P = _audit_rows(rec_kind, T)
+    if rec.shape[1] < P:
+        raise ValueError(f"rec holds {rec.shape[1]} rows per cell, T = {T} needs {P}")
+    if P and (rec.shape[1] != P or not rec.is_contiguous()):
+        rec = rec[:, :P].contiguous()       # rows of a longer horizon's buffer
+    if allow is None:
+        pass
+    elif torch.is_tensor(allow):
+        if (allow.dtype != torch.int64 or tuple(allow.shape) != (C,) or allow.device != dev
+                or not allow.is_contiguous()):
+            raise ValueError(f"allow must be a contiguous int64 [{C}] tensor on {dev}")
+    else:
+        host = np.asarray(allow, np.int64).reshape(-1)
+        if host.shape[0] != C or (C and host.min() < 0):
+            raise ValueError(f"allow must hold {C} counts >= 0")
+        allow = torch.as_tensor(host, device=dev)
+    need = int(lib.ccmpc_ideal_risk_quantile_workspace_bytes(T, int(rec_kind), C))
+    if need == 0:
+        raise ValueError(f"ccmpc_ideal_risk_quantile rejects T = {T}, rec_kind = {rec_kind}, "
+                         f"n_cells = {C}")
+    status = None
+    if out is None:
+        status = torch.empty(C, dtype=torch.int32, device=dev)
+        out = RiskQuantile(torch.empty((C, P), dtype=torch.float64, device=dev),
+                           torch.empty((C, P), dtype=torch.float64, device=dev),
+                           torch.empty((C, P), dtype=torch.int32, device=dev),
+                           torch.empty(need, dtype=torch.uint8, device=dev))
+    else:
+        if not isinstance(out, RiskQuantile):
+            out, status = out
+            if (status.dtype != torch.int32 or tuple(status.shape) != (C,)
+                    or not status.is_contiguous()):
+                raise ValueError(f"status must be a contiguous int32 [{C}] tensor")
+        for name in ("q", "rhs", "status"):
+            t = getattr(out, name)
+            if t is None or tuple(t.shape) != (C, P) or not t.is_contiguous():
+                raise ValueError(f"out.{name} must be a contiguous {(C, P)} tensor")
+        if out.workspace is None or out.workspace.numel() < need:
+            raise ValueError(f"out.workspace must hold {need} bytes")
+    if C == 0:
+        return out, status
+    _lib.check(lib.ccmpc_ideal_risk_quantile(
+        _p(prev_mean), _p(prev_cov), T_src, _p(src_cell), C, T, n_samples, _p(x0),
+        int(seed) & (2**64 - 1), _p(seed_dev), _p(rng_cell),
+        # no rows (T = 1 half-space kinds): rec is only checked to be non-null
+        _p(rec) if P else _p(prev_mean), int(rec_kind), float(R), _p(allow),
+        _p(out.workspace), out.workspace.numel(), _p(out.q), _p(out.rhs), _p(out.status),
+        _p(status), _stream()), "ccmpc_ideal_risk_quantile")
+    return out, status
+
+
 def calibrated_records(rec, rec_kind, quant, mode="replace"):
     """A new uint8 tensor of `rec`'s layout whose rhs field (d of the half-space record, rhs of
     the affine record and of the compact packing) carries risk_quantile's offsets; `rec` itself

@@ -1889,7 +1889,8 @@ class MidlevelAgent:
         risk.allow_counts(...) particles of each cell open at the record's step, for the per-step
         budget eps / O / ph (eps default: risk.EPS_TOTAL; R default: the agent's).  Needs the
         frame's records to have been generated from that store, i.e. Tsh == ph (below ph they
-        come from the ideal rollout, which is never materialised: raises RuntimeError).  The
+        come from the ideal rollout, which is never materialised: raises RuntimeError;
+        calibrate_ideal_constraints serves those frames).  The
         store must be read before the next step of the same shape (raises after it), as for
         audit_plan.  Never called implicitly and changes no planner state.
         Returns risk.calibration_report's dict; with mode ("replace", "tighten" or "relax") a
@@ -1902,7 +1903,8 @@ class MidlevelAgent:
         scene.check_live()
         if last is None:
             raise RuntimeError(f"the last frame (Tsh = {T} < ph) has no materialised records: "
-                               "its half-spaces come from the ideal rollout")
+                               "its half-spaces come from the ideal rollout "
+                               "(calibrate_ideal_constraints calibrates them on it)")
         kind = last[1]
         rec = engine._rec_bytes(last[0], kind, scene.store.n_cells)
         eps = risk.EPS_TOTAL if eps is None else float(eps)
@@ -1911,6 +1913,47 @@ class MidlevelAgent:
         allow = risk.allow_counts(counts, K, ph, eps)
         quant = engine.risk_quantile(scene.store, rec, kind, allow=allow,
                                      R=self.R if R is None else float(R), T=T)
+        report = risk.calibration_report(quant, engine.record_fields(rec, kind),
+                                         counts, K, ph, eps)
+        if mode is None:
+            return report
+        return report, engine.calibrated_records(rec, kind, quant, mode)
+
+    def calibrate_ideal_constraints(self, R=None, eps=None, mode=None):
+        """Monte-Carlo calibration of the frame's records on the ideal rollout they were built
+        from (engine.ideal_risk_quantile): the counterpart of calibrate_constraints for the
+        frames audit_ideal_plan serves (the eager Minkowski and affine-tangent generators and
+        predict_and_constrain, each at Tsh < ph; RuntimeError after any other frame).  The
+        n_ideal samples of the frame's own rollout are regenerated on the device in every
+        counting pass, never materialised; the offsets leave at most
+        risk.allow_counts([n_ideal] * C, ...) of them open at the record's step, for the
+        per-step budget eps / O / ph (eps default: risk.EPS_TOTAL; R default: the agent's).
+        After predict_and_constrain the records live in the step graph's buffers, so they must
+        be calibrated before the next step of the same shape (raises after it).  Never called
+        implicitly and changes no planner state.
+        Returns risk.calibration_report's dict; with mode ("replace", "tighten" or "relax") a
+        pair (report, records): engine.calibrated_records' device tensor in the layout
+        ccmpc_mpc_qp reads, the frame's own records left as they are."""
+        if self._ideal_audit_src is None:
+            raise RuntimeError("the last frame's records were not built from the ideal rollout: "
+                               "call a Minkowski or affine-tangent generator at Tsh < ph first")
+        pm, pc, src, seed, T, K, last, scene = self._ideal_audit_src
+        if scene is not None:
+            scene.check_live()
+        dev = self.device
+        pm = torch.as_tensor(pm, device=dev)
+        pc = torch.as_tensor(pc, device=dev)
+        src = torch.as_tensor(src, dtype=torch.int32, device=dev)
+        C = len(src)
+        kind = last[1]
+        rec = engine._rec_bytes(last[0], kind, C)
+        eps = risk.EPS_TOTAL if eps is None else float(eps)
+        ph = self.prediction_horizon
+        counts = [self.n_ideal] * C
+        allow = risk.allow_counts(counts, K, ph, eps)
+        quant, _ = engine.ideal_risk_quantile(pm, pc, src, T, self.n_ideal, rec, kind,
+                                              allow=allow, R=self.R if R is None else float(R),
+                                              seed=seed)
         report = risk.calibration_report(quant, engine.record_fields(rec, kind),
                                          counts, K, ph, eps)
         if mode is None:

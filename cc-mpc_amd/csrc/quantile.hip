@@ -241,53 +241,6 @@ __global__ __launch_bounds__(kQuantThreads) void quantile_count_kernel(QuantArgs
   }
 }
 
-// The smallest u (as its key) for which the audit's predicate protects a particle with
-// s = side*q under rhs = side*u; the key of +inf where no double does.
-__device__ __forceinline__ uint64_t quant_offset_key(double q, double sd, double r2n) {
-  auto pred = [&](uint64_t k) {
-    const double u = quant_unkey(k);
-    const double rhs = sd * u, s = sd * q;
-    return audit_protects(sd * (rhs - s), r2n);
-  };
-  uint64_t lo = kKeyNegInf, hi = kKeyPosInf;
-  if (!pred(hi)) return hi;
-  if (pred(lo)) return lo;
-  // invariant: !pred(lo), pred(hi), lo < hi
-  const double est = q + sqrt(r2n);
-  if (isfinite(est)) {
-    const uint64_t ke = quant_key(est);
-    if (pred(ke)) {
-      hi = ke;
-      for (int i = 0; i < 4; ++i) {
-        if (hi - 1 > lo && pred(hi - 1)) {
-          --hi;
-        } else {
-          lo = hi - 1;
-          break;
-        }
-      }
-    } else {
-      lo = ke;
-      for (int i = 0; i < 4; ++i) {
-        if (lo + 1 < hi && !pred(lo + 1)) {
-          ++lo;
-        } else {
-          hi = lo + 1;
-          break;
-        }
-      }
-    }
-  }
-  while (hi - lo > 1) {  // at most 64 halvings
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (pred(mid))
-      hi = mid;
-    else
-      lo = mid;
-  }
-  return hi;
-}
-
 // q and the offset of record i from q's key.
 __device__ __forceinline__ void quant_finish(const QuantArgs &a, int64_t i, const QuantRec &q,
                                              uint64_t key) {

@@ -820,6 +820,60 @@ int ccmpc_risk_quantile(const void *positions, int dtype, int64_t ld, int64_t T,
                         int32_t *out_status, ccmpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The same calibration on the samples of the ideal rollout, which are never materialised: the
+ * counterpart of ccmpc_ideal_risk_audit for the question "which offset would meet the budget on
+ * the samples this shrinking-horizon frame's records were built from?".
+ *
+ * The contract: out_q, out_rhs and out_status equal, bit for bit, those of ccmpc_ideal_rollout
+ * (Z = NULL, the same prev_mean, prev_cov, T_src, src_cell, T, n_samples, x0, seed and rng_cell)
+ * followed by ccmpc_risk_quantile on that store with cell_cnt[c] = n_samples for every cell and
+ * the same rec, rec_kind, R and cell_allow.  The rollout would cost 16 T n_samples bytes per
+ * cell; this call regenerates every sample in registers in each counting pass (a sample is a
+ * pure function of (seed, rng_cell[c], i, t) and the source moments) and needs only the
+ * workspace of ccmpc_ideal_risk_quantile_workspace_bytes(T, rec_kind, n_cells), which returns 0
+ * for arguments the call rejects.
+ * Rollout arguments as ccmpc_ideal_risk_audit: seed_dev (device memory, nullable) overrides
+ * seed, rng_cell NULL = stream c, x0 nullable.  Record arguments and cell_allow as
+ * ccmpc_risk_quantile: the same fields read, the same definition of a calibrated record, the
+ * same w, q and u*; N = n_samples for every cell, so m >= n_samples gives CCMPC_CAL_VACUOUS and
+ * a negative cell_allow[c], found on the device, CCMPC_CAL_SKIPPED.
+ *
+ * Failed cells, which the store call leaves unspecified ("positions are assumed finite"), are
+ * defined here.  Let f(c) be the first step whose samples are NaN: 0 if the initial draw fails,
+ * else the smallest t for which the step's conditional cannot be built (the codes of
+ * out_cell_status), else T.  A record of cell c with step t >= f(c) is CCMPC_CAL_SKIPPED
+ * (out_q = NaN, out_rhs = the record's own rhs); records with t < f(c) are calibrated and the
+ * sentence above holds for them: their samples are finite and are the rollout's bits.
+ *  out_cell_status[c]  int32, nullable: the rollout's status.
+ * Sharding invariance as ccmpc_ideal_risk_audit: the cells of one call give the same outputs as
+ * the same cells in several calls with the matching rng_cell, src_cell, x0, rec and cell_allow
+ * slices.
+ *
+ * CCMPC_ERR_ARG, all checked before any device call: T_src outside [2, 40], T outside
+ * [1, T_src - 1], n_cells outside [0, 65536), n_samples outside [1, 2^32), R not finite or
+ * <= 0, an unknown rec_kind, rec NULL, a NULL out_q, out_rhs or out_status where P > 0, a
+ * workspace that is too small or not 16-byte aligned.  n_cells == 0 returns CCMPC_OK, as does
+ * P == 0 (T = 1 of the half-space kinds), which writes at most out_cell_status.
+ * The call is capturable: it never synchronises, never reads device memory on the host, and
+ * needs neither an initialised workspace nor initialised outputs.  The launch sequence is fixed
+ * by (T, rec_kind, n_cells, n_samples): the first launch, then 8 x (a counting pass that
+ * generates the samples, a narrowing launch).  A record whose selected bin holds few enough
+ * samples has them hand their whole keys over in the next pass and is resolved from that list
+ * (the rank-th largest, ties included: a function of the multiset only); passes in which no
+ * record of a workgroup is live generate nothing.  Integer atomics only: no output bit depends
+ * on execution order.  Do not share one workspace between concurrent streams.
+ * ------------------------------------------------------------------------------------- */
+size_t ccmpc_ideal_risk_quantile_workspace_bytes(int64_t T, int rec_kind, int64_t n_cells);
+int ccmpc_ideal_risk_quantile(const double *prev_mean, const double *prev_cov, int64_t T_src,
+                              const int32_t *src_cell, int64_t n_cells, int64_t T,
+                              int64_t n_samples, const double *x0, uint64_t seed,
+                              const uint64_t *seed_dev, const int32_t *rng_cell,
+                              const void *rec, int rec_kind, double R,
+                              const int64_t *cell_allow, void *workspace, size_t workspace_bytes,
+                              double *out_q, double *out_rhs, int32_t *out_status,
+                              int32_t *out_cell_status, ccmpc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Box-face chance constraints (the "TCST" family): the second-order-cone row data of
  * compute_obstacle_constraints_GMM (v8ideal/__init__.py:966-1094, "nominal"),
  * compute_robust_constraints_GMM (:1096-1229, "robust") and
